@@ -23,6 +23,11 @@ HIP-event timings taken inside the timed steps on the stream the kernels run on.
 
 Contract: `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line on rank 0.  Started without a launcher
 and N > 1 it starts `python -m torch.distributed.run` itself (before anything touches the GPU) and relays the line.
+Such a plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, the step's event
+times in `components`, `roofline`, `roofline_issue`, `roofline_sweep`).  Everything else -- the end-to-end CLI runs and the compiled
+reference beside them, the CPU baseline, the other EM mode, the EM stress (configs[4]), the K4 probe, the configs[3] leg,
+the strong-scaled leg, the two-stream pipeline and the checksums against the reference-derived rows -- runs with --full.
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (see write_outputs).
 """
 import argparse
 import hashlib
@@ -77,7 +82,18 @@ def parse_args():
     ap.add_argument("--config3-nseq", type=int, default=12_500_000, help="sequences per rank in the configs[3] leg")
     ap.add_argument("--strong", type=int, default=1,
                     help="1: also run the line's sequence set STRONG-scaled (split over the ranks; components.config2_strong); 0: skip")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the timed step (CPU baseline, end to end, other EM mode, configs[3] / [4], K4, "
+                         "strong scaling, pipeline, checks against the reference); the options that tune those legs act only with it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the tables and PWMs of the last timed step as DIR/<name>.npy (float32 / float64, rank 0)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:  # a plain run: the step and its headline only
+        args.no_e2e = args.no_cpu_baseline = True
+        args.pipelined = args.em_stress_pwms = args.k4_patterns = args.config3_steps = args.strong = 0
+    return args
 
 
 def relaunch_under_torchrun(args):
@@ -157,7 +173,29 @@ def golden_row(W, nseq, L, both, world):
     return None
 
 
-def run_leg(rt, W, both, L, nseq, P_total, em_iters, steps, warmup, em_fast, seq0=None, local_only=False, row=None):
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_SAMPLE = 1 << 19
+
+
+def write_outputs(out_dir, arrays):
+    """`--dump-outputs`: every array as out_dir/<name>.npy, float32 kept, everything else as float64 (the integer tables
+    are below 2^53: exact).  If all of them together pass 64 MiB (W >= 12), every array longer than DUMP_SAMPLE
+    elements is replaced by the same fixed sample of its flattened entries: DUMP_SAMPLE flat indices drawn without
+    replacement by numpy's default_rng(0), ascending -- the same for every run and every build at that size."""
+    conv = {k: np.ascontiguousarray(v, dtype=np.float32 if v.dtype == np.float32 else np.float64) for k, v in arrays.items()}
+    if sum(v.nbytes for v in conv.values()) > DUMP_BUDGET_BYTES:
+        for k, v in conv.items():
+            if v.size > DUMP_SAMPLE:
+                idx = np.sort(np.random.default_rng(0).choice(v.size, size=DUMP_SAMPLE, replace=False))
+                conv[k] = v.reshape(-1)[idx]
+    assert sum(v.nbytes for v in conv.values()) <= DUMP_BUDGET_BYTES
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in conv.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+
+
+def run_leg(rt, W, both, L, nseq, P_total, em_iters, steps, warmup, em_fast, seq0=None, local_only=False, row=None,
+            check=True, dump_dir=None):
     """One configuration through the whole step, `warmup` untimed + `steps` timed passes bracketed by barriers:
     K1(+K1b) count -> C1 exchange -> mirror, V -> K2+K3 sweep -> K5 EM on this rank's share of P_total seed PWMs.
     This rank holds sequences [seq0, seq0 + nseq) of the seed-1 set (default: rank * nseq, the weak-scaling layout).
@@ -165,7 +203,8 @@ def run_leg(rt, W, both, L, nseq, P_total, em_iters, steps, warmup, em_fast, seq
     every rank on its own (the denominator of a strong-scaling figure).  row = (n_per_shard, k): the reference-derived
     row the tables are to be compared with (default: this layout's, (nseq, world)).
     Returns the tables, HIP-event times per component, the wall time of the timed steps (max over ranks) and the checks:
-    sha256 of what the ranks hold after the exchange, compared with that row."""
+    sha256 of what the ranks hold after the exchange, compared with that row (None when `check` is off).
+    dump_dir: rank 0 writes what the last timed step computed there (write_outputs) before anything else runs."""
     torch, pk, lib, C, ctx, dist = rt.torch, rt.pk, rt.lib, rt.C, rt.ctx, rt.dist
     rank, world, dev = rt.rank, rt.world, rt.dev
     NP, K = 4 ** W, 2
@@ -270,8 +309,21 @@ def run_leg(rt, W, both, L, nseq, P_total, em_iters, steps, warmup, em_fast, seq
             acc[k] += ctx.elapsed_ms(ev[k][0], ev[k][1])
     barrier()
     dt = max_over_ranks(rt, time.perf_counter() - t0)
+    if dump_dir and rank == 0:
+        h_scal = scal.cpu().numpy()
+        write_outputs(dump_dir, {"counts": counts.cpu().numpy().view(np.uint32), "bg_counts": h_scal[:84], "ltot": h_scal[84:],
+                                 "bg_model_V": V.cpu().numpy(), "bgprob": bgprob.cpu().numpy(), "expected": expected.cpu().numpy(),
+                                 "logp": logp.cpu().numpy(), "z": z.cpu().numpy(), "em_pwms": pwms[:n_my].cpu().numpy(),
+                                 "em_state": em_state[:n_my].cpu().numpy(), "em_change": em_change[:n_my].cpu().numpy()})
 
-    # ---- checks (outside the timed region, always): what the ranks hold after the exchange.  `checks` is what a 1-rank
+    leg.__dict__.update(dict(counts=counts, scal=scal, V=V, bgprob=bgprob, expected=expected, logp=logp, z=z, pwms=pwms, pw_init=pw_init,
+                             em_state=em_state, em_change=em_change, words=words, items=items, ni=ni, n_my=n_my, my_pwms=my_pwms,
+                             alpha=alpha, acc=acc, dt=dt, exchange=exchange, step=step, seed_pwms=seed_pwms, checks=None,
+                             checks_ok=None, barrier=barrier))
+    if not check:
+        return leg
+
+    # ---- checks (outside the timed region): what the ranks hold after the exchange.  `checks` is what a 1-rank
     #      run of the same global set must reproduce bit for bit (serial EM: no batching effects); `checks_ok` compares it
     #      with the reference-derived row for this (W, size, world), if one was computed
     ctx.set_option("em_fast", 2)
@@ -301,11 +353,7 @@ def run_leg(rt, W, both, L, nseq, P_total, em_iters, steps, warmup, em_fast, seq
                  "bg_counters": h_scal[:84].tolist() == row["bgcounts"], "z": checks["sha_z"] == row["sha_z"]}
         checks_ok = {"ok": all(parts.values()), "parts": parts,
                      "against": "tests/golden/shard_prefix_checksums.json[%s, k=%d]: the compiled reference's per-shard tables added (z: the oracle's sweep on those sums)" % (row["job"], row["k"])}
-
-    leg.__dict__.update(dict(counts=counts, scal=scal, V=V, bgprob=bgprob, expected=expected, logp=logp, z=z, pwms=pwms, pw_init=pw_init,
-                             em_state=em_state, em_change=em_change, words=words, items=items, ni=ni, n_my=n_my, my_pwms=my_pwms,
-                             alpha=alpha, acc=acc, dt=dt, exchange=exchange, step=step, seed_pwms=seed_pwms, checks=checks,
-                             checks_ok=checks_ok, barrier=barrier))
+    leg.checks, leg.checks_ok = checks, checks_ok
     return leg
 
 
@@ -629,7 +677,8 @@ def main():
     rt.rank, rt.world, rt.multi, rt.rccl_ranks, rt.args = rank, world, multi, rccl_ranks, args
 
     with torch.cuda.stream(ctx_stream):
-        leg = run_leg(rt, W, both, L, nseq, args.pwms, args.em_iters, args.steps, args.warmup, args.em_fast)
+        leg = run_leg(rt, W, both, L, nseq, args.pwms, args.em_iters, args.steps, args.warmup, args.em_fast, check=args.full,
+                      dump_dir=args.dump_outputs)
         # (names the rest of main() reads)
         counts, scal, V, bgprob, expected, logp, z = leg.counts, leg.scal, leg.V, leg.bgprob, leg.expected, leg.logp, leg.z
         pwms, pw_init, em_state, em_change = leg.pwms, leg.pw_init, leg.em_state, leg.em_change
@@ -659,7 +708,7 @@ def main():
 
         # the other EM mode on the step's own PWM batch, for the record
         other_mode = 1 if args.em_fast == 2 else 2
-        em_other_ms = time_em(other_mode, n_my, pw_init, pwms, em_state, em_change)
+        em_other_ms = time_em(other_mode, n_my, pw_init, pwms, em_state, em_change) if args.full else None
 
         # ---- EM-only stress, BASELINE configs[4] as SURVEY.md 8(d) defines it: PLUS count table of this input, the
         #      highest-count k-mers (ties by ascending id) as seeds, threshold 0, all iterations ----------------------
@@ -831,8 +880,9 @@ def main():
                     "note": "reference-parity mode: every cell's 4^(W-1) float32 additions in the reference's order (as a wave-wide scan whose blocks are evaluated ahead of the chain, csrc/seqsum.h); the throughput mode above is pinned to the fp64 oracle within 1e-5, not to the reference's own rounding"}
         # what the ranks hold after the exchange (sha256) and whether that is what the compiled reference's per-shard
         # tables add up to for this (W, size, N) -- at every N, so that a multi-GPU line verifies itself
-        out["checks"] = checks
-        out["checks_ok"] = checks_ok
+        if args.full:
+            out["checks"] = checks
+            out["checks_ok"] = checks_ok
         if pipelined is not None:
             out["components"]["pipelined"] = pipelined
         if config3 is not None:
@@ -872,6 +922,16 @@ def main():
         ctx.close()
     if multi:
         dist.destroy_process_group()
+
+
+def host_threads():
+    """Threads for the host-side legs: the cores this process may run on (a one-GPU lease is a share of the host), not
+    the host's hardware threads, and no more than OMP_NUM_THREADS where that is set."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    if omp.isdigit() and int(omp) > 0:
+        n = min(n, int(omp))
+    return max(1, n)
 
 
 def mem_available_gb():
@@ -1068,8 +1128,7 @@ def cpu_baseline(args, W, both, L, stress_probe=None):
     t_stats = (time.perf_counter() - t0) / nsweep
     # the same two sweeps with all cores: the loops the reference runs under OpenMP (src/base_pattern.cpp:232,253,261,289);
     # count and EM are serial in the reference whatever --threads says
-    # (the cores this process may run on -- a one-GPU lease is a share of the host --, not the host's hardware threads)
-    ncores = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    ncores = host_threads()
     po.set_threads(ncores)
     try:
         po.stats(W, counts, bgp[2], ltot)
@@ -1180,7 +1239,7 @@ def reference_cli_phases(W, both, L, n=300_000):
         fa = os.path.join(tmp, "s.fa")
         _write_sample_fasta(fa, n, L)
         res = {}
-        cores = os.cpu_count() or 1
+        cores = host_threads()
         for threads in (1, cores):
             t0 = time.perf_counter()
             p = subprocess.Popen([exe, fa, "-w", str(W), "--strand", "BOTH" if both else "PLUS", "--threads", str(threads), "-o",

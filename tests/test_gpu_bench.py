@@ -19,7 +19,7 @@ def last_json(out):
 
 
 def test_single_rank_json_contract():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--nseq", "200000",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--nseq", "200000",
                         "--cpu-sample-seqs", "20000", "--em-stress-pwms", "32", "--config3-nseq", "50000", "--config3-steps", "2",
                         "--e2e-runs", "3"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
@@ -83,6 +83,44 @@ def test_single_rank_json_contract():
     assert al["threads"] >= 1 and al["zscores_per_s"] > 0 and al["bgprob_tables_3_orders_s"] > 0
 
 
+def test_plain_run_is_lean_and_dumps_what_its_last_step_computed(tmp_path):
+    """Without --full the line carries the timed step and nothing else; --dump-outputs writes the last timed step's tables
+    and PWMs, the same bits as a --full run of the same arguments writes, and the sha256 checks of that --full run (taken
+    on the ranks' tables after the timed steps) are those of the dumped arrays."""
+    import hashlib
+
+    import numpy as np
+
+    def run(extra, out):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--nseq", "200000",
+                            "--dump-outputs", str(out)] + extra, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+        assert r.returncode == 0, r.stderr.decode()[-2000:]
+        return last_json(r.stdout)
+    plain = run([], tmp_path / "plain")
+    full = run(["--full", "--em-stress-pwms", "0", "--k4-patterns", "0", "--no-cpu-baseline", "--no-e2e", "--config3-steps", "0"], tmp_path / "full")
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert plain[key] is not None and (key in ("value", "ms_per_step") or plain[key] == full[key]), key
+    assert plain["steps"] == 3 and abs(plain["value"] - 200000 * 200 / (plain["ms_per_step"] * 1e-3) / 1e9) < 1e-2 * plain["value"]
+    assert plain["components"]["count_ms"] > 0 and plain["components"]["em_ms"] > 0
+    assert "checks" not in plain and "cpu_baseline" not in plain and "roofline_em" not in plain and "roofline_k4" not in plain
+    assert plain["components"]["em_other_mode_ms"] is None and plain["components"]["em_stress_ms"] is None
+    assert not {"e2e_cli", "pipelined", "config3", "config4", "config2_strong"} & set(plain["components"])
+    assert full["components"]["pipelined"]["same_bits_as_the_sequential_passes"] is True
+    names = ("counts", "bg_counts", "ltot", "bg_model_V", "bgprob", "expected", "logp", "z", "em_pwms", "em_state", "em_change")
+    got = {}
+    for n in names:
+        a, b = np.load(str(tmp_path / "plain" / (n + ".npy"))), np.load(str(tmp_path / "full" / (n + ".npy")))
+        assert a.dtype in (np.float32, np.float64) and a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), n
+        got[n] = a
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    assert got["counts"].shape == (4 ** 10,) and got["em_pwms"].shape == (16, 10, 4) and int(got["ltot"][0]) == 200000 * 191
+    ck = full["checks"]
+    assert hashlib.sha256(got["counts"].astype(np.uint32).tobytes()).hexdigest() == ck["sha_counts"]
+    assert hashlib.sha256(got["z"].tobytes()).hexdigest() == ck["sha_z"]
+    assert hashlib.sha256(np.concatenate([got["bg_counts"], got["ltot"]]).astype(np.int64).tobytes()).hexdigest() == ck["sha_bg_ltot"]
+    assert hashlib.sha256("".join(p.tobytes().hex() for p in got["em_pwms"]).encode()).hexdigest() == ck["sha_em_pwms"]
+
+
 def test_two_rank_rehearsal_allreduces_the_tables():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -90,7 +128,7 @@ def test_two_rank_rehearsal_allreduces_the_tables():
     s.close()
     env = dict(os.environ, PENGK_BENCH_BACKEND="gloo")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-                        "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2",
+                        "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2",
                         "--warmup", "1", "--nseq", "150000", "--em-stress-pwms", "8", "--config3-steps", "0"], stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, env=env, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
@@ -104,7 +142,7 @@ def test_two_rank_rehearsal_allreduces_the_tables():
 
 
 def _bench(extra, env=None, launcher=None):
-    cmd = ([sys.executable] + (launcher or []) + [os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--em-stress-pwms", "0",
+    cmd = ([sys.executable] + (launcher or []) + [os.path.join(ROOT, "bench.py"), "--full", "--steps", "1", "--warmup", "1", "--em-stress-pwms", "0",
                                                   "--k4-patterns", "0", "--no-cpu-baseline", "--no-e2e", "--config3-steps", "0"] + extra)
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
@@ -283,7 +321,7 @@ def _full_size_bench(gpus, env=None):
     port_s.close()
     cmd = [sys.executable] + (["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(gpus), "--master-addr", "127.0.0.1",
                                "--master-port", str(port)] if env else []) + \
-        [os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "2", "--warmup", "1", "--em-stress-pwms", "64", "--k4-patterns", "0",
+        [os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(gpus), "--steps", "2", "--warmup", "1", "--em-stress-pwms", "64", "--k4-patterns", "0",
          "--no-cpu-baseline", "--no-e2e", "--config3-steps", "2"]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=1200)
     assert r.returncode == 0, r.stderr.decode()[-3000:]

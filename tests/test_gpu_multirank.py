@@ -116,9 +116,10 @@ def test_two_ranks_on_a_synthetic_set_and_their_memory(tmp_path):
     assert strip_timing(res[0][2]) == strip_timing(se) and res[1][1] == b""
     # memory: with the staged path (PENGK_NO_STREAMING=1), which holds a shard's byte codes to the end -- the streaming
     # path gives every chunk's codes back as soon as they are packed, and its peak says little about the shard
-    # Every figure is the SMALLER peak of three runs: a process's peak carries transients that have nothing to do with its
+    # Every figure is the MEDIAN peak of three runs: a process's peak carries transients that have nothing to do with its
     # shard (allocator arenas of the reader's threads, the HIP runtime's staging buffers: +100 MB one run in three on a
-    # busy box), and they only ever add.
+    # busy box), and they go both ways (a rank on the small file peaked at 637 MB once beside 826 / 826 MB, which the
+    # smaller of the three turned into a growth of 257 MB against the usual ~70): one run off in either direction is outvoted.
     keep = {"PENGK_NO_STREAMING": "1"}
     REPEATS = 3
     peaks = {"whole": [], "whole_small": [], "ranks": [[], []], "base": [[], []]}
@@ -133,9 +134,9 @@ def test_two_ranks_on_a_synthetic_set_and_their_memory(tmp_path):
         for rank in range(2):
             peaks["ranks"][rank].append(peak_rss_mb(ranks[rank][2]))
             peaks["base"][rank].append(peak_rss_mb(base[rank][2]))
-    grow_plain = min(peaks["whole"]) - min(peaks["whole_small"])
+    grow_plain = np.median(peaks["whole"]) - np.median(peaks["whole_small"])
     for rank in range(2):
-        grow = min(peaks["ranks"][rank]) - min(peaks["base"][rank])
+        grow = np.median(peaks["ranks"][rank]) - np.median(peaks["base"][rank])
         # one process: file text + codes + packed stream for 270k more records; a rank: for 135k more
         assert grow < 0.65 * grow_plain, (rank, grow, grow_plain, peaks)
 
