@@ -309,6 +309,61 @@ int pengk_sequential_sum_f32(pengk_ctx* ctx, const float* d_terms, uint64_t n_ch
 int pengk_motif_similarity(pengk_ctx* ctx, int n, const float* h_pwm, const float* h_comp, const int32_t* h_len,
                            const uint64_t* h_sites, int both_strands, const float* h_bg, int first_new, float* h_out);
 
+/* ---- motif scoring against sampled background sequences (the second user-facing step of the reference's wrapper
+ *      scripts/shoot_peng.py, which runs BaMMmotif2's FDR tool and an R script over peng_motif's output; this library's
+ *      metric is its own) ---------------------------------------------------------------------------
+ * Scan layout of real sequences (NOT the packed layout above, which keeps only the runs the count visits and no
+ * sequence identity): sequence i starts at base h_offs[i], a multiple of 32, in a 2-bit stream of uint64 words (base g in
+ * bits [2(g%32), 2(g%32)+2) of word g/32; A,C,G,T = 0..3, any other letter stored as 0), has h_lens[i] bases and owns the
+ * ceil(len/32) words from h_offs[i]/32 on; valid[g/32] bit g%32 is 1 iff base g is A/C/G/T (0 beyond the sequence's end).
+ * The sampled background sequences use the same words layout (same offsets and lengths) with every base valid.
+ * Replaces the per-motif sequence scans of scripts/shoot_peng.py's FDR call. */
+#define PENGK_SCORE_SENTINEL (-2147483647 - 1) /* best score of a sequence without a window of A/C/G/T only */
+
+/* Words a set of n_seq sequences takes (codes offsets h_code_offs[0..n_seq], as pengk_pack): sum of ceil(len/32). */
+int pengk_scan_layout_words(const int64_t* h_code_offs, int64_t n_seq, uint64_t* n_words);
+/* Host builder (pure CPU; scripts/shoot_peng.py hands FASTA files to the FDR tool instead): byte codes (0 = other,
+ * A,C,G,T = 1..4) of n_seq sequences -> their words / validity words from word `word0` on, h_offs[i] / h_lens[i] for
+ * i < n_seq.  Disjoint batches of a set (e.g. the chunks of the FASTA reader) may be built from several threads at once
+ * into one set of arrays; each writes only the words it owns. */
+int pengk_scan_layout_build(const uint8_t* h_codes, const int64_t* h_code_offs, int64_t n_seq, uint64_t word0,
+                            uint64_t* h_words, uint32_t* h_valid, int64_t* h_offs, uint32_t* h_lens);
+/* The synthetic input of pengk_synth_sequences (same splitmix64 stream: sequences [seq0, seq0+n_seq) of length L) in the
+ * scan layout: d_words / d_valid n_seq * ceil(L/32) entries, d_offs / d_lens n_seq entries. */
+int pengk_synth_scan_sequences(pengk_ctx* ctx, uint64_t seed, uint64_t seq0, uint64_t n_seq, uint32_t L, uint64_t* d_words,
+                               uint32_t* d_valid, int64_t* d_offs, uint32_t* d_lens);
+/* Negatives of scripts/shoot_peng.py (its `--negN` random sequences), one per input sequence, sampled on the device from
+ * an order-K background model (K <= 2) straight into d_words in the layout given by d_offs / d_lens (every base valid):
+ * position p of the sequence with GLOBAL index seq0 + i draws r = mix64(seed + 0x9E3779B97F4A7C15 * (((seq0 + i) << 32)
+ * + p + 1)) >> 32 (mod 2^64; mix64 = the splitmix64 finalizer) and takes base (r >= T0) + (r >= T1) + (r >= T2) with
+ * the thresholds of its context -- the previous min(p, K) sampled bases.  h_thresholds: uint32 triples for the contexts
+ * of orders 0..K back to back (1 + 4 + 16 triples at K = 2), a context of order k indexed like the background model's
+ * V[k] (big-endian: the older base more significant); T_b = floor(c_b * 2^32) clamped to 2^32 - 1, c_b the cumulative
+ * conditional probability of bases 0..b.  seq0 makes shards of a multi-process run sample what one process samples. */
+int pengk_sample_background(pengk_ctx* ctx, uint64_t seed, uint64_t seq0, uint64_t n_seq, const int64_t* d_offs,
+                            const uint32_t* d_lens, int K, const uint32_t* h_thresholds, uint64_t* d_words);
+/* Best window score of every motif on every sequence (the ZOOPS scan of scripts/shoot_peng.py's FDR call):
+ * h_S = n_motifs x PENGK_MAX_MOTIF_LEN x 4 int32 log-odds (rows beyond h_len[m] unused), 1 <= h_len[m] <=
+ * PENGK_MAX_MOTIF_LEN, |S| <= 2000.  d_best[m * n_seq + i] = max over the windows of sequence i whose bases are all
+ * valid of sum_j S[m][j][base] -- with both_strands also of the reverse-complement matrix S[m][w-1-j][3-a] --,
+ * PENGK_SCORE_SENTINEL without such a window.  d_valid = NULL: every base of a sequence is valid (sampled sequences).
+ * Motifs are scanned in groups whose tables fit in LDS: each base is read from HBM once per group. */
+int pengk_motif_scan(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_valid, const int64_t* d_offs,
+                     const uint32_t* d_lens, uint64_t n_seq, int n_motifs, const int32_t* h_S, const int32_t* h_len,
+                     int both_strands, int32_t* d_best);
+/* Histograms of d_best (n_motifs x n_seq, as pengk_motif_scan wrote it), ADDED to d_hist (uint64, caller-zeroed): motif m
+ * owns h_nbins[m] = h_hi[m] - h_lo[m] + 2 bins from d_hist + h_hist_offs[m] on -- bin 0 the sentinel, bin 1 + s - h_lo[m]
+ * score s (scores outside [lo, hi] are clamped into it; lo / hi = the sums of the column minima / maxima of S).  Integer
+ * sums: histograms of shards and of several calls add exactly (scripts/shoot_peng.py's FDR tool keeps score lists). */
+int pengk_score_histograms(pengk_ctx* ctx, int n_motifs, const int32_t* d_best, uint64_t n_seq, const int32_t* h_lo,
+                           const int32_t* h_hi, const uint64_t* h_hist_offs, uint64_t* d_hist);
+/* Pure CPU: the two numbers scripts/shoot_peng.py adds to every motif, from the input (h_pos) and background (h_neg)
+ * histograms of one motif (nbins bins, ascending scores, the sentinel bin lowest).  zoops_score = AUC =
+ * sum_s P[s] * (2 Nneg_below(s) + N[s]) / (2 Npos Nneg) (numerator in int64; PENGK_ERR_RANGE above 2^62);
+ * occur = clamp((TPR - FPR) / (1 - FPR), 0, 1) at the smallest threshold t with 100 Nneg_ge(t) <= Nneg (0 if FPR == 1).
+ * This project's metric, not BaMMmotif2's AvRec. */
+int pengk_score_summary(const uint64_t* h_pos, const uint64_t* h_neg, uint64_t nbins, double* zoops_out, double* occur_out);
+
 /* Self-test of the division sequence the serial EM's weights kernel uses where a PWM's operand ranges allow (the IEEE
  * division's instructions without its range scaling: csrc/em.hip, lean_div; src/peng.cpp:124-125, 186 are the three
  * divisions of a weight).  4096 x 256 threads draw pairs_per_thread random operand pairs each, keep those inside the

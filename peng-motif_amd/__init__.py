@@ -31,7 +31,11 @@ EXPORTS = [
     "pengk_allreduce_tables", "pengk_comm_check_bin_bound", "pengk_allgather",
     "pengk_comm_host_init_env", "pengk_comm_host_info", "pengk_comm_host_allgather", "pengk_comm_host_allreduce_u64",
     "pengk_comm_host_shutdown",
+    "pengk_scan_layout_words", "pengk_scan_layout_build", "pengk_synth_scan_sequences", "pengk_sample_background",
+    "pengk_motif_scan", "pengk_score_histograms", "pengk_score_summary",
 ]
+MAX_MOTIF_LEN = 64
+SCORE_SENTINEL = -2 ** 31
 
 
 class PengkError(RuntimeError):
@@ -118,6 +122,13 @@ def lib():
         L.pengk_comm_host_allgather.argtypes = [vp, vp, C.c_size_t]
         L.pengk_comm_host_allreduce_u64.argtypes = [vp, C.c_size_t]
         L.pengk_comm_host_shutdown.argtypes = []
+        L.pengk_scan_layout_words.argtypes = [vp, i64, C.POINTER(u64)]
+        L.pengk_scan_layout_build.argtypes = [vp, vp, i64, u64, vp, vp, vp, vp]
+        L.pengk_synth_scan_sequences.argtypes = [vp, u64, u64, u64, C.c_uint32, vp, vp, vp, vp]
+        L.pengk_sample_background.argtypes = [vp, u64, u64, u64, vp, vp, C.c_int, vp, vp]
+        L.pengk_motif_scan.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, vp, vp, C.c_int, vp]
+        L.pengk_score_histograms.argtypes = [vp, C.c_int, vp, u64, vp, vp, vp, vp]
+        L.pengk_score_summary.argtypes = [vp, vp, u64, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         _lib = L
     return _lib
 
@@ -149,6 +160,34 @@ class Packed:
             self.all_whole = int(st.all_whole)
         finally:
             lib().pengk_packed_free(C.byref(st))
+
+
+class ScanLayout:
+    """Host result of pengk_scan_layout_build: the scan layout of the motif scoring (include/pengk.h)."""
+
+    def __init__(self, codes, offs):
+        codes = np.ascontiguousarray(codes, np.uint8)
+        offs = np.ascontiguousarray(offs, np.int64)
+        n = len(offs) - 1
+        nw = C.c_uint64()
+        _check(lib().pengk_scan_layout_words(offs.ctypes.data, n, C.byref(nw)))
+        self.n_seq = n
+        self.words = np.zeros(max(nw.value, 1), np.uint64)
+        self.valid = np.zeros(max(nw.value, 1), np.uint32)
+        self.offs = np.zeros(max(n, 1), np.int64)
+        self.lens = np.zeros(max(n, 1), np.uint32)
+        _check(lib().pengk_scan_layout_build(codes.ctypes.data, offs.ctypes.data, n, 0, self.words.ctypes.data,
+                                             self.valid.ctypes.data, self.offs.ctypes.data, self.lens.ctypes.data))
+
+
+def score_summary(pos_hist, neg_hist):
+    """(zoops_score, occur) of one motif from its input / background histograms (pengk_score_summary, CPU)."""
+    p = np.ascontiguousarray(pos_hist, np.uint64)
+    n = np.ascontiguousarray(neg_hist, np.uint64)
+    assert p.shape == n.shape
+    z, o = C.c_double(), C.c_double()
+    _check(lib().pengk_score_summary(p.ctypes.data, n.ctypes.data, len(p), C.byref(z), C.byref(o)))
+    return z.value, o.value
 
 
 class DeviceArray:
@@ -351,6 +390,57 @@ class Context:
         d_o = DeviceArray.from_host(self, np.zeros(max(t.shape[0], 1), np.float32))
         _check(lib().pengk_sequential_sum_f32(self.h, _ptr(d_t) if d_t is not None else None, t.shape[0], t.shape[1], _ptr(d_o)))
         return d_o.to_host()[:t.shape[0]]
+
+    # ---- motif scoring (scripts/shoot_peng.py's second step) -------------------------------------------------
+    def upload_scan(self, layout):
+        """device copy of a ScanLayout: (words, valid, offs, lens, n_seq)"""
+        return (self.to_device(layout.words), self.to_device(layout.valid), self.to_device(layout.offs),
+                self.to_device(layout.lens), layout.n_seq)
+
+    def synth_scan(self, seed, seq0, n_seq, L):
+        """pengk_synth_sequences' input in the scan layout: (words, valid, offs, lens, n_seq)"""
+        nw = n_seq * ((L + 31) // 32)
+        words, valid = self.empty(max(nw, 1), np.uint64), self.empty(max(nw, 1), np.uint32)
+        offs, lens = self.empty(max(n_seq, 1), np.int64), self.empty(max(n_seq, 1), np.uint32)
+        _check(lib().pengk_synth_scan_sequences(self.h, seed, seq0, n_seq, L, _ptr(words), _ptr(valid), _ptr(offs), _ptr(lens)))
+        return words, valid, offs, lens, n_seq
+
+    def sample_background(self, scan, seed, seq0, K, thresholds, words=None):
+        """negatives in the words layout of `scan` (device); thresholds: uint32 triples of the contexts of orders 0..K"""
+        th = np.ascontiguousarray(thresholds, np.uint32).reshape(-1)
+        assert len(th) == 3 * (1, 5, 21)[K]
+        if words is None:
+            words = self.empty(scan[0].shape, np.uint64)
+        _check(lib().pengk_sample_background(self.h, seed, seq0, scan[4], _ptr(scan[2]), _ptr(scan[3]), K, th.ctypes.data,
+                                             _ptr(words)))
+        return words
+
+    def motif_scan(self, scan, S, lens, both, words=None, all_valid=False, best=None):
+        """best[m, i] of every motif on every sequence of `scan`; S: n x w x 4 int32 (padded to MAX_MOTIF_LEN here)"""
+        n = len(lens)
+        Sp = np.zeros((max(n, 1), MAX_MOTIF_LEN, 4), np.int32)
+        for m in range(n):
+            Sp[m, :lens[m]] = np.asarray(S[m], np.int32)[:lens[m]]
+        ln = np.ascontiguousarray(lens, np.int32)
+        if best is None:
+            best = self.empty((max(n, 1), max(scan[4], 1)), np.int32)
+        _check(lib().pengk_motif_scan(self.h, _ptr(words if words is not None else scan[0]), None if all_valid else _ptr(scan[1]),
+                                      _ptr(scan[2]), _ptr(scan[3]), scan[4], n, Sp.ctypes.data, ln.ctypes.data, int(both),
+                                      _ptr(best)))
+        return best
+
+    def score_histograms(self, best, n_seq, lo, hi, hist=None):
+        """add the histograms of best (n_motifs x n_seq, device) to hist (device uint64; allocated zeroed if None);
+        returns (hist, offsets)"""
+        lo = np.ascontiguousarray(lo, np.int32)
+        hi = np.ascontiguousarray(hi, np.int32)
+        nb = hi.astype(np.int64) - lo + 2
+        offs = np.concatenate([[0], np.cumsum(nb)]).astype(np.uint64)
+        if hist is None:
+            hist = self.to_device(np.zeros(int(offs[-1]), np.uint64))
+        _check(lib().pengk_score_histograms(self.h, len(lo), _ptr(best), n_seq, lo.ctypes.data, hi.ctypes.data,
+                                            offs.ctypes.data, _ptr(hist)))
+        return hist, offs
 
     def em_device(self, W, n_pwm, d_pwms, counts, bg, d_state, d_change, saturation=1e4, threshold=0.08, max_iterations=10):
         _check(lib().pengk_em_device(self.h, W, n_pwm, _ptr(d_pwms), saturation, threshold, max_iterations, _ptr(counts),

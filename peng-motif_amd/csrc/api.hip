@@ -150,6 +150,7 @@ int pengk_destroy(pengk_ctx* ctx) {
   if (ctx->d_bg_partials) (void)hipFree(ctx->d_bg_partials);
   if (ctx->d_count_aux) (void)hipFree(ctx->d_count_aux);
   if (ctx->d_sim) (void)hipFree(ctx->d_sim);
+  if (ctx->d_score) (void)hipFree(ctx->d_score);
   if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
   return PENGK_OK;

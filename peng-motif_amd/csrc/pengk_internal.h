@@ -66,6 +66,8 @@ struct pengk_ctx {
   int scatter_blocks_per_cu = 0; // tuning hook: workgroups per CU of the partitioned scan (0 = default)
   void* d_sim = nullptr;         // motif similarity grid: PWMs | complements | lengths | sites | scores
   size_t sim_bytes = 0;
+  void* d_score = nullptr;       // motif scoring: chunk tables | motif records | group records (score.hip)
+  size_t score_bytes = 0;
   void* comm = nullptr;          // RCCL communicator (comm.hip)
   int comm_transport = 0;        // PENGK_TRANSPORT_*: how the tables of a multi-rank run are exchanged
   int comm_rank = 0, comm_world = 1;

@@ -42,12 +42,15 @@ int Global::device = 0;
 bool Global::filter_neighbors = true;
 unsigned Global::minimum_processed_motifs = 0;
 int Global::maximum_optimized_patterns = 50;
+bool Global::scoreMotifs = false;
+unsigned long long Global::scoreSeed = 1;
 
 void Global::init(int nargs, char* args[]) {
   readArguments(nargs, args);
   Alphabet::init(alphabetType);
   pengk_host::start_context();  // the device runtime starts while the FASTA files are read
   pengk_host::start_sharded_ingest();  // multi-GPU run: every rank reads its own byte range of the files
+  pengk_host::keep_host_codes(scoreMotifs);  // (the scoring scans the input after the motifs are found)
   // both strands are handled inside the count; sequences are always read single stranded
   // ... and every chunk of the input set is packed and sent to the device while the rest is still being read
   pengk_host::begin_streaming_pack(patternLength);
@@ -185,6 +188,10 @@ void Global::readArguments(int nargs, char* args[]) {
       minimum_processed_motifs = std::stoi(need(i, nargs, args, printHelp));
     } else if (!strcmp(a, "--max-optimized-patterns")) {
       maximum_optimized_patterns = std::stoi(need(i, nargs, args, printHelp));
+    } else if (!strcmp(a, "--score-motifs")) {
+      scoreMotifs = true;
+    } else if (!strcmp(a, "--score-seed")) {
+      scoreSeed = std::stoull(need(i, nargs, args, printHelp));
     } else if (!strcmp(a, "--version")) {
       std::cout << "peng_motif " << VERSION_NUMBER << std::endl;  // (src/Global.cpp:299-301: without the word)
       exit(0);
@@ -224,6 +231,9 @@ void Global::printHelp() {
   printf("  --no-neighbor-filtering        keep Hamming-1 neighbours of selected seeds\n");
   printf("  --minimum-processed-patterns INT   (default 0)\n");
   printf("  --max-optimized-patterns INT       (default 50)\n");
+  printf("  --score-motifs                 score every motif against as many sequences sampled from the background\n");
+  printf("                                 model (zoops_score = AUC, occur) and rank the motifs by it\n");
+  printf("  --score-seed INT               seed of the sampled sequences (default 1)\n");
   printf("  --threads INT                  accepted for compatibility\n");
   printf("  --device INT                   HIP device index (default 0)\n");
   printf("  -v INT                         verbosity\n");

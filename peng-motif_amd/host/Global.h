@@ -57,6 +57,9 @@ class Global {
   static unsigned minimum_processed_motifs;  // --minimum-processed-patterns
   static int maximum_optimized_patterns;     // --max-optimized-patterns
 
+  static bool scoreMotifs;                   // --score-motifs (new: scripts/shoot_peng.py's scoring step, on the device)
+  static unsigned long long scoreSeed;       // --score-seed
+
   static void init(int nargs, char* args[]);
   static void destruct();
 

@@ -261,6 +261,8 @@ void sink_begin(void* user, size_t range_bytes, size_t n_chunks) {
   st->uploader = std::thread(upload_loop, st);
 }
 
+bool g_keep_host_codes = false;
+
 // (returns true: the chunk's byte codes are packed, the reader may give them back)
 bool sink_chunk(void* user, size_t, const SequenceChunk& c) {
   Stream* st = (Stream*)user;
@@ -289,9 +291,11 @@ bool sink_chunk(void* user, size_t, const SequenceChunk& c) {
     }
   }
   if (filled) st->cv.notify_one();
-  return true;
+  return !g_keep_host_codes;
 }
 }  // namespace
+
+void keep_host_codes(bool keep) { g_keep_host_codes = keep; }
 
 void begin_streaming_pack(int W) {
   if (W < PENGK_MIN_W || W > PENGK_MAX_W) return;  // (Peng::process ends such a run with the reference's message)

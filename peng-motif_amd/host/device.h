@@ -51,6 +51,9 @@ struct PackedInput {
 void begin_streaming_pack(int W);                              // the NEXT SequenceSet constructed is packed as it is read
 const PackedInput* finish_streaming_pack(::SequenceSet* set);    // waits for the last upload; nullptr if nothing was packed
 const PackedInput* packed_input(::SequenceSet* set, int W);      // of a set that went through the two calls above, else nullptr
+// the packed chunks keep their byte codes on the host (the motif scoring builds its own layout from them afterwards);
+// call before begin_streaming_pack
+void keep_host_codes(bool keep);
 
 // PENGK_TIMING=1: wall-clock report of sub-phases on stderr (stdout stays the reference's trace)
 struct Lap {

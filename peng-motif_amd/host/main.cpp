@@ -12,6 +12,7 @@
 #include "Global.h"
 #include "device.h"
 #include "iupac_pattern.h"
+#include "motif_score.h"
 #include "peng.h"
 
 namespace {
@@ -99,9 +100,29 @@ int main(int nargs, char** args) {
   peng.process(params, result);
   clock.lap("process (count, sweep, hill-climb, PWMs, EM, merging)");
   peng.filter_redundancy(Global::mergeBitfactorThreshold, result);
+  std::vector<MotifScore> scores;
+  if (Global::scoreMotifs) {
+    // the writers' order first, then stable by zoops_score descending (scripts/shoot_peng.py re-ranks the motifs so)
+    std::sort(result.begin(), result.end(), sort_IUPAC_patterns);
+    scores = score_motifs(result, *Global::inputSequenceSet, *bgModel, Global::bgModelOrder,
+                          Global::strand == Strand::BOTH_STRANDS, Global::scoreSeed);
+    std::vector<size_t> order(result.size());
+    for (size_t i = 0; i < order.size(); ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return scores[a].zoops_score > scores[b].zoops_score; });
+    std::vector<IUPACPattern*> r2;
+    std::vector<MotifScore> s2;
+    for (size_t i : order) {
+      r2.push_back(result[i]);
+      s2.push_back(scores[i]);
+    }
+    result.swap(r2);
+    scores.swap(s2);
+    clock.lap("score");
+  }
+  const std::vector<MotifScore>* sc = Global::scoreMotifs ? &scores : nullptr;
   if (pengk_host::rank() == 0) {
-    if (Global::outputFilename) peng.printShortMeme(result, Global::outputFilename, bgModel);
-    if (Global::jsonFilename) peng.printJson(result, Global::jsonFilename, VERSION_NUMBER, bgModel);
+    if (Global::outputFilename) peng.printShortMeme(result, Global::outputFilename, bgModel, sc);
+    if (Global::jsonFilename) peng.printJson(result, Global::jsonFilename, VERSION_NUMBER, bgModel, sc);
   }
 
   for (IUPACPattern* p : result) delete p;

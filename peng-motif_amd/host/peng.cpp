@@ -519,9 +519,10 @@ void Peng::filter_iupac_patterns(size_t pattern_length, size_t minimum_retained_
 }
 
 // ---- writers (src/peng.cpp:602-728) ----------------------------------------------------------------------------------
-void Peng::printShortMeme(std::vector<IUPACPattern*>& pats, const std::string output_filename, BackgroundModel* bg) {
+void Peng::printShortMeme(std::vector<IUPACPattern*>& pats, const std::string output_filename, BackgroundModel* bg,
+                          const std::vector<MotifScore>* scores) {
   const unsigned PRECISION = 8;
-  std::sort(pats.begin(), pats.end(), sort_IUPAC_patterns);
+  if (!scores) std::sort(pats.begin(), pats.end(), sort_IUPAC_patterns);
   std::ofstream out(output_filename);
   if (!out.is_open()) {
     std::cerr << "Unable to open output file (" << output_filename << ")!";
@@ -533,11 +534,15 @@ void Peng::printShortMeme(std::vector<IUPACPattern*>& pats, const std::string ou
   out << "Background letter frequencies" << std::endl;
   for (size_t i = 0; i < strlen(alphabet); ++i) out << (i ? " " : "") << alphabet[i] << " " << bg->getV()[0][i];
   out << std::endl << std::endl;
-  for (IUPACPattern* p : pats) {
+  for (size_t n = 0; n < pats.size(); ++n) {
+    IUPACPattern* p = pats[n];
     out << "MOTIF " << p->get_pattern_string() << std::endl;
     out << "letter-probability matrix:" << " alength= " << 4 << " w= " << p->get_pattern_length() << " nsites= " << p->get_sites()
         << " bg_prob= " << p->get_bg_p() << " opt_bg_order= " << p->get_optimization_bg_model_order()
-        << " log(Pval)= " << p->getLogPval() << std::endl;
+        << " log(Pval)= " << p->getLogPval();
+    // (scripts/shoot_peng.py's write_meme: the two fields behind log(Pval))
+    if (scores) out << " zoops_score= " << (*scores)[n].zoops_score << " occur= " << (*scores)[n].occur;
+    out << std::endl;
     float** pwm = p->get_pwm();
     no_zero_pwm(pwm, (unsigned)p->get_pattern_length(), PRECISION);
     for (size_t w = 0; w < p->get_pattern_length(); ++w) {
@@ -549,9 +554,9 @@ void Peng::printShortMeme(std::vector<IUPACPattern*>& pats, const std::string ou
 }
 
 void Peng::printJson(std::vector<IUPACPattern*>& pats, const std::string output_filename, const std::string,
-                     BackgroundModel* bg) {
+                     BackgroundModel* bg, const std::vector<MotifScore>* scores) {
   const unsigned PRECISION = 8;
-  std::sort(pats.begin(), pats.end(), sort_IUPAC_patterns);
+  if (!scores) std::sort(pats.begin(), pats.end(), sort_IUPAC_patterns);
   std::ofstream out(output_filename);
   if (!out.is_open()) {
     std::cerr << "Unable to open output file (" << output_filename << ")!";
@@ -574,6 +579,10 @@ void Peng::printJson(std::vector<IUPACPattern*>& pats, const std::string output_
     out << "\t\t\t\"log(Pval)\" : " << p->getLogPval() << "," << std::endl;
     out << "\t\t\t\"bg_prob\" : " << p->get_bg_p() << "," << std::endl;
     out << "\t\t\t\"opt_bg_order\" : " << p->get_optimization_bg_model_order() << "," << std::endl;
+    if (scores) {
+      out << "\t\t\t\"zoops_score\" : " << (*scores)[n].zoops_score << "," << std::endl;
+      out << "\t\t\t\"occur\" : " << (*scores)[n].occur << "," << std::endl;
+    }
     out << "\t\t\t\"pwm\" : [" << std::endl;
     float** pwm = p->get_pwm();
     no_zero_pwm(pwm, (unsigned)p->get_pattern_length(), PRECISION);

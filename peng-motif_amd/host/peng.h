@@ -13,6 +13,7 @@
 
 #include "Global.h"
 #include "iupac_pattern.h"
+#include "motif_score.h"
 #include "shared/Alphabet.h"
 #include "shared/BackgroundModel.h"
 #include "shared/SequenceSet.h"
@@ -45,10 +46,11 @@ class Peng {
 
   void process(PengParameters& params, std::vector<IUPACPattern*>& best_iupac_patterns);
   void filter_redundancy(const float merge_bit_factor_threshold, std::vector<IUPACPattern*>& iupac_patterns);
+  // scores (--score-motifs): one per pattern, in the order given, which the writers then keep
   void printShortMeme(std::vector<IUPACPattern*>& best_iupac_patterns, const std::string output_filename,
-                      BackgroundModel* bg_model);
+                      BackgroundModel* bg_model, const std::vector<MotifScore>* scores = nullptr);
   void printJson(std::vector<IUPACPattern*>& best_iupac_patterns, const std::string output_filename,
-                 const std::string version_number, BackgroundModel* bg_model);
+                 const std::string version_number, BackgroundModel* bg_model, const std::vector<MotifScore>* scores = nullptr);
 
  private:
   BackgroundModel* bg_model;
