@@ -74,7 +74,8 @@ int pengk_set_stream(pengk_ctx* ctx, void* hip_stream);
  * histograms (W = 8 .. 14); "n_windows_hint" = total windows of the attached items (sizes the key buffer
  * tightly; set it after pengk_set_sequences); "key_cap_override" (test hook) entries per bucket region of the
  * partitioned count, 0 = automatic; "sweep_pairs" 1 (default) / 0: both strands from W = 12 on, a pattern and its reverse complement evaluated once (0: one thread per pattern; same bits); "iupac_group_bytes" (test hook) scratch budget for one group of large
- * patterns in pengk_iupac_aggregate, 0 = 1 GiB; "em_fast" 2 (default) / 1 / 0, see pengk_em.  Info: "deferred_items" (of the last pengk_count;
+ * patterns in pengk_iupac_aggregate, 0 = 1 GiB; "em_fast" 2 (default) / 1 / 0, see pengk_em; "sites_record_budget" records per slice of pengk_sites_slices
+ * (default 2^24, also readable through pengk_get_info).  Info: "deferred_items" (of the last pengk_count;
  * synchronises), "num_cu"; of the last pengk_em / pengk_em_device call in the serial mode with its blocks evaluated ahead
  * (synchronise): "em_fetched_blocks" (blocks a chain added term by term), "em_mispredicted_blocks" (of those: blocks
  * whose estimated binade did not hold), "em_restaged_blocks" / "em_restaged_waits" (csrc/seqsum.h, WalkCounts). */
@@ -363,6 +364,50 @@ int pengk_score_histograms(pengk_ctx* ctx, int n_motifs, const int32_t* d_best, 
  * occur = clamp((TPR - FPR) / (1 - FPR), 0, 1) at the smallest threshold t with 100 Nneg_ge(t) <= Nneg (0 if FPR == 1).
  * This project's metric, not BaMMmotif2's AvRec. */
 int pengk_score_summary(const uint64_t* h_pos, const uint64_t* h_neg, uint64_t nbins, double* zoops_out, double* occur_out);
+
+/* ---- motif sites (--sites: every occurrence of the found motifs, with an exact p-value; this project's own) ----------
+ * Over the scan layout above and the integer log-odds h_S / h_len of pengk_motif_scan: a site of motif m is a window
+ * strand whose bases are all valid and whose score (sum_j S[m][j][base], on the - strand with S_rc[j][a] = S[w-1-j][3-a],
+ * scored only with both_strands) is >= h_thr[m].  After the thresholds everything is integer: any slicing, any rank
+ * count and a numpy restatement give the same set.
+ * Three steps: pengk_sites_count, pengk_sites_slices (cuts the sequences into slices whose records fit a budget), then
+ * pengk_sites_emit once per slice. */
+#define PENGK_SITES_BLOCK 4096 /* sequences per block total of pengk_sites_slices */
+typedef struct {
+  uint32_t seq;          /* sequence index within the slice (global index - i0) */
+  uint32_t pos;          /* 0-based first base of the window */
+  int32_t score;         /* integer log-odds on the matched strand */
+  uint32_t motif_strand; /* motif index * 2 + strand (0 = +, 1 = -) */
+} pengk_site;
+
+/* Pure CPU.  P(score >= t) for one strand of one window of motif S (w x 4 int32, |S| <= 2000) whose bases are drawn
+ * independently from h_bg (4 float32, taken as double), for every t in [lo, hi] (the sums of the column minima /
+ * maxima, returned in lo_out / hi_out): h_tail[t - lo], hi - lo + 1 entries (NULL: only lo / hi).  Exact DP over the
+ * integer scores in a fixed order: q_0 = delta(0); q_{j+1}[t] = sum over a = 0, 1, 2, 3 in this order of
+ * q_j[t - S[j][a]] * bg[a], each from 0.0 (terms outside q_j's range skipped); the tail summed sequentially from hi down. */
+int pengk_score_tail_pvalues(const int32_t* h_S, int w, const float* h_bg, int32_t* lo_out, int32_t* hi_out, double* h_tail);
+/* Pure CPU.  The smallest integer t in [lo, hi] with h_tail[t - lo] <= p (0 < p <= 1), else hi + 1 (no window reaches it). */
+int pengk_score_threshold(const double* h_tail, int32_t lo, int32_t hi, double p, int32_t* t_out);
+/* Sites of every motif on every sequence: d_counts[m * n_seq + i] (uint64), the number of window strands of sequence i
+ * with score >= h_thr[m].  h_thr: n_motifs int32 (hi + 1 and above: none).  Other arguments as pengk_motif_scan. */
+int pengk_sites_count(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_valid, const int64_t* d_offs,
+                      const uint32_t* d_lens, uint64_t n_seq, int n_motifs, const int32_t* h_S, const int32_t* h_len,
+                      int both_strands, const int32_t* h_thr, uint64_t* d_counts);
+/* From d_counts (pengk_sites_count): h_motif_totals[m] = the sites of motif m over all sequences, and the slices
+ * [h_bounds[k], h_bounds[k + 1]) of the sequences, k < *n_slices, in order, covering [0, n_seq), with h_records[k] records
+ * each.  A slice is as long as its records stay within the option "sites_record_budget" (default 2^24; >= 1, a test
+ * hook can force many slices) and at most 2^31 sequences; a single sequence above the budget is a slice of its own.
+ * Only the first max_slices slices are written (h_bounds: max_slices + 1 entries); *n_slices is always the full count,
+ * so a caller with too small arrays calls again.  Synchronises with the stream. */
+int pengk_sites_slices(pengk_ctx* ctx, const uint64_t* d_counts, uint64_t n_seq, int n_motifs, uint64_t* h_motif_totals,
+                       uint64_t max_slices, uint64_t* h_bounds, uint64_t* h_records, uint64_t* n_slices);
+/* The sites of sequences [i0, i1) (at most 2^31 of them) as records in d_sites, in this order: motif index, sequence,
+ * window position, + before -.  The same arguments as pengk_sites_count, whose d_counts fix every record's place: the
+ * slice's records are sum over m, i of d_counts[m * n_seq + i]; none at or beyond cap is written. */
+int pengk_sites_emit(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_valid, const int64_t* d_offs,
+                     const uint32_t* d_lens, uint64_t n_seq, int n_motifs, const int32_t* h_S, const int32_t* h_len,
+                     int both_strands, const int32_t* h_thr, const uint64_t* d_counts, uint64_t i0, uint64_t i1,
+                     pengk_site* d_sites, uint64_t cap);
 
 /* Self-test of the division sequence the serial EM's weights kernel uses where a PWM's operand ranges allow (the IEEE
  * division's instructions without its range scaling: csrc/em.hip, lean_div; src/peng.cpp:124-125, 186 are the three

@@ -33,9 +33,12 @@ EXPORTS = [
     "pengk_comm_host_shutdown",
     "pengk_scan_layout_words", "pengk_scan_layout_build", "pengk_synth_scan_sequences", "pengk_sample_background",
     "pengk_motif_scan", "pengk_score_histograms", "pengk_score_summary",
+    "pengk_score_tail_pvalues", "pengk_score_threshold", "pengk_sites_count", "pengk_sites_slices", "pengk_sites_emit",
 ]
 MAX_MOTIF_LEN = 64
 SCORE_SENTINEL = -2 ** 31
+SITES_BLOCK = 4096
+SITE = np.dtype([("seq", np.uint32), ("pos", np.uint32), ("score", np.int32), ("motif_strand", np.uint32)])
 
 
 class PengkError(RuntimeError):
@@ -129,6 +132,11 @@ def lib():
         L.pengk_motif_scan.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, vp, vp, C.c_int, vp]
         L.pengk_score_histograms.argtypes = [vp, C.c_int, vp, u64, vp, vp, vp, vp]
         L.pengk_score_summary.argtypes = [vp, vp, u64, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.pengk_score_tail_pvalues.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp]
+        L.pengk_score_threshold.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, C.POINTER(C.c_int32)]
+        L.pengk_sites_count.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, vp, vp, C.c_int, vp, vp]
+        L.pengk_sites_slices.argtypes = [vp, vp, u64, C.c_int, vp, u64, vp, vp, C.POINTER(u64)]
+        L.pengk_sites_emit.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, vp, vp, C.c_int, vp, vp, u64, u64, vp, u64]
         _lib = L
     return _lib
 
@@ -188,6 +196,33 @@ def score_summary(pos_hist, neg_hist):
     z, o = C.c_double(), C.c_double()
     _check(lib().pengk_score_summary(p.ctypes.data, n.ctypes.data, len(p), C.byref(z), C.byref(o)))
     return z.value, o.value
+
+
+def score_tail_pvalues(S, bg):
+    """(lo, tail): tail[t - lo] = P(score >= t) of one window strand of S (w x 4 int32) under bg (pengk_score_tail_pvalues, CPU)"""
+    S = np.ascontiguousarray(S, np.int32)
+    bg = np.ascontiguousarray(bg, np.float32)
+    lo, hi = C.c_int32(), C.c_int32()
+    _check(lib().pengk_score_tail_pvalues(S.ctypes.data, S.shape[0], bg.ctypes.data, C.byref(lo), C.byref(hi), None))
+    tail = np.zeros(hi.value - lo.value + 1, np.float64)
+    _check(lib().pengk_score_tail_pvalues(S.ctypes.data, S.shape[0], bg.ctypes.data, C.byref(lo), C.byref(hi), tail.ctypes.data))
+    return lo.value, tail
+
+
+def score_threshold(tail, lo, p):
+    """the smallest t with tail[t - lo] <= p, else lo + len(tail) (pengk_score_threshold, CPU)"""
+    tail = np.ascontiguousarray(tail, np.float64)
+    t = C.c_int32()
+    _check(lib().pengk_score_threshold(tail.ctypes.data, lo, lo + len(tail) - 1, p, C.byref(t)))
+    return t.value
+
+
+def _pad_motifs(S, lens):
+    n = len(lens)
+    Sp = np.zeros((max(n, 1), MAX_MOTIF_LEN, 4), np.int32)
+    for m in range(n):
+        Sp[m, :lens[m]] = np.asarray(S[m], np.int32)[:lens[m]]
+    return Sp, np.ascontiguousarray(lens, np.int32)
 
 
 class DeviceArray:
@@ -441,6 +476,68 @@ class Context:
         _check(lib().pengk_score_histograms(self.h, len(lo), _ptr(best), n_seq, lo.ctypes.data, hi.ctypes.data,
                                             offs.ctypes.data, _ptr(hist)))
         return hist, offs
+
+    # ---- motif sites (--sites) ------------------------------------------------------------------------------
+    def sites_count(self, scan, S, lens, both, thr, counts=None):
+        """counts[m, i] (device uint64): sites of motif m on sequence i of `scan` at thresholds thr"""
+        n = len(lens)
+        Sp, ln = _pad_motifs(S, lens)
+        th = np.ascontiguousarray(thr, np.int32)
+        if counts is None:
+            counts = self.empty((max(n, 1), max(scan[4], 1)), np.uint64)
+        _check(lib().pengk_sites_count(self.h, _ptr(scan[0]), _ptr(scan[1]), _ptr(scan[2]), _ptr(scan[3]), scan[4], n,
+                                       Sp.ctypes.data, ln.ctypes.data, int(both), th.ctypes.data, _ptr(counts)))
+        return counts
+
+    def sites_slices(self, counts, n_seq, n_motifs):
+        """(bounds, records, motif_totals) of pengk_sites_slices"""
+        tot = np.zeros(max(n_motifs, 1), np.uint64)
+        cap = 64
+        while True:
+            bounds, recs, ns = np.zeros(cap + 1, np.uint64), np.zeros(cap, np.uint64), C.c_uint64()
+            _check(lib().pengk_sites_slices(self.h, _ptr(counts), n_seq, n_motifs, tot.ctypes.data, cap, bounds.ctypes.data,
+                                            recs.ctypes.data, C.byref(ns)))
+            if ns.value <= cap:
+                k = ns.value
+                return bounds[:k + 1] if k else np.zeros(1, np.uint64), recs[:k], tot[:n_motifs]
+            cap = ns.value
+
+    def sites_emit(self, scan, S, lens, both, thr, counts, i0, i1, out, cap):
+        Sp, ln = _pad_motifs(S, lens)
+        th = np.ascontiguousarray(thr, np.int32)
+        _check(lib().pengk_sites_emit(self.h, _ptr(scan[0]), _ptr(scan[1]), _ptr(scan[2]), _ptr(scan[3]), scan[4], len(lens),
+                                      Sp.ctypes.data, ln.ctypes.data, int(both), th.ctypes.data, _ptr(counts), i0, i1,
+                                      _ptr(out) if out is not None else None, cap))
+
+    def motif_sites(self, scan, S, lens, both, thr):
+        """every site, in the --sites order (motif, global sequence, position, + before -): a SITE array whose seq field
+        is the global sequence index (uint64 here), plus the count pass's per-motif totals"""
+        n_seq, n = scan[4], len(lens)
+        counts = self.sites_count(scan, S, lens, both, thr)
+        bounds, recs, tot = self.sites_slices(counts, n_seq, n)
+        cap = int(recs.max()) if len(recs) else 0
+        buf = self.empty(max(cap, 1) * SITE.itemsize, np.uint8)
+        parts = []
+        for k in range(len(recs)):
+            i0, i1 = int(bounds[k]), int(bounds[k + 1])
+            self.sites_emit(scan, S, lens, both, thr, counts, i0, i1, buf, cap)
+            r = buf.to_host()[:int(recs[k]) * SITE.itemsize].view(SITE)
+            parts.append((i0, r))
+        out = np.zeros(int(sum(len(r) for _, r in parts)),
+                       [("motif", np.int64), ("seq", np.uint64), ("pos", np.uint32), ("strand", np.uint8), ("score", np.int32)])
+        # slices are sequence ranges; within one, motif-major: gather motif by motif over the slices
+        j = 0
+        for m in range(n):
+            for i0, r in parts:
+                sel = r[(r["motif_strand"] >> 1) == m]
+                k = len(sel)
+                out["motif"][j:j + k] = m
+                out["seq"][j:j + k] = sel["seq"].astype(np.uint64) + np.uint64(i0)
+                out["pos"][j:j + k] = sel["pos"]
+                out["strand"][j:j + k] = sel["motif_strand"] & 1
+                out["score"][j:j + k] = sel["score"]
+                j += k
+        return out, tot
 
     def em_device(self, W, n_pwm, d_pwms, counts, bg, d_state, d_change, saturation=1e4, threshold=0.08, max_iterations=10):
         _check(lib().pengk_em_device(self.h, W, n_pwm, _ptr(d_pwms), saturation, threshold, max_iterations, _ptr(counts),

@@ -151,6 +151,7 @@ int pengk_destroy(pengk_ctx* ctx) {
   if (ctx->d_count_aux) (void)hipFree(ctx->d_count_aux);
   if (ctx->d_sim) (void)hipFree(ctx->d_sim);
   if (ctx->d_score) (void)hipFree(ctx->d_score);
+  if (ctx->d_sites) (void)hipFree(ctx->d_sites);
   if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
   return PENGK_OK;
@@ -222,6 +223,11 @@ int pengk_set_option(pengk_ctx* ctx, const char* name, int64_t value) {
     ctx->iupac_group_bytes = (uint64_t)value;
     return PENGK_OK;
   }
+  if (strcmp(name, "sites_record_budget") == 0) {
+    if (value < 1) return fail(PENGK_ERR_ARG, "sites_record_budget must be >= 1 record");
+    ctx->sites_record_budget = (uint64_t)value;
+    return PENGK_OK;
+  }
   if (strcmp(name, "scatter_blocks_per_cu") == 0) {
     if (value < 0 || value > 8) return fail(PENGK_ERR_ARG, "scatter_blocks_per_cu must be 0 (default) .. 8");
     ctx->scatter_blocks_per_cu = (int)value;
@@ -244,6 +250,10 @@ int pengk_get_info(pengk_ctx* ctx, const char* name, int64_t* value) {
       PENGK_HIP(hipStreamSynchronize(ctx->stream));
     }
     *value = n;
+    return PENGK_OK;
+  }
+  if (strcmp(name, "sites_record_budget") == 0) {
+    *value = (int64_t)ctx->sites_record_budget;
     return PENGK_OK;
   }
   if (strcmp(name, "num_cu") == 0) {

@@ -68,6 +68,9 @@ struct pengk_ctx {
   size_t sim_bytes = 0;
   void* d_score = nullptr;       // motif scoring: chunk tables | motif records | group records (score.hip)
   size_t score_bytes = 0;
+  void* d_sites = nullptr;       // motif sites: per-sequence | per-block | per-motif totals, or a slice's record offsets | tile sums
+  size_t sites_bytes = 0;
+  uint64_t sites_record_budget = 1ull << 24;  // records per slice of pengk_sites_slices (a larger sequence: a slice of its own)
   void* comm = nullptr;          // RCCL communicator (comm.hip)
   int comm_transport = 0;        // PENGK_TRANSPORT_*: how the tables of a multi-rank run are exchanged
   int comm_rank = 0, comm_world = 1;

@@ -6,6 +6,9 @@
 //   scan           motif groups whose 4-mer chunk tables fit in LDS; one thread per sequence slides a 64-base look-ahead
 //                  buffer over its words, so chunk c of the window is byte c of the buffer
 //   histograms     per-motif integer histograms of the best scores (LDS bins for the top of the range, global beyond)
+//   sites          (--sites) the scan's walk again with per-motif thresholds: a count pass, block totals
+//                  that cut the sequences into slices of bounded records, an exclusive scan of a slice's counts and an
+//                  emit pass that writes every site at its place
 #include <string.h>
 
 #include <algorithm>
@@ -51,6 +54,92 @@ __device__ __forceinline__ uint32_t byte_of(uint32_t b0, uint32_t b1, uint32_t b
   return (v >> (8 * (c & 3))) & 0xFFu;
 }
 
+// The scan loop every scan kernel shares: one sequence (its words wp, validity words vp -- NULL: every base valid -- and
+// length L) walked under the nrec motifs of a group.  For each pass of SCAN_PASS motifs: v.begin(q, r) for the pass's
+// slots q (r = r0 + q, the group record; slots q >= np get the pass's first record), v.window(q, pos, sf, sr) for every
+// window at base pos whose bases are all valid (sf the + score; sr the - score, computed with BOTH only), v.end(q, r)
+// for the slots q < np.
+template <bool BOTH, class Visit>
+__device__ __forceinline__ void walk_sequence(const uint64_t* wp, const uint32_t* vp, uint32_t L,
+                                              const int32_t* tab, const MotifRec* mrec, int nrec, Visit& v) {
+  const uint32_t nw = (L + 31u) >> 5;
+  auto ldw = [&](uint32_t j) -> uint64_t { return j < nw ? wp[j] : 0ull; };
+  auto ldv = [&](uint32_t j) -> uint32_t {
+    if (j >= nw) return 0u;
+    if (vp) return vp[j];
+    const uint32_t rem = L - 32u * j;
+    return rem >= 32u ? 0xFFFFFFFFu : ((1u << rem) - 1u);
+  };
+  // SCAN_PASS motifs per pass over the sequence: the buffer's upkeep per base is shared by them
+  for (int r0 = 0; r0 < nrec; r0 += SCAN_PASS) {
+    const int np = nrec - r0 < SCAN_PASS ? nrec - r0 : SCAN_PASS;
+    uint64_t wmask[SCAN_PASS];
+    int nch[SCAN_PASS];
+    const int32_t* tf[SCAN_PASS];
+    int wmin = PENGK_MAX_MOTIF_LEN;
+#pragma unroll
+    for (int q = 0; q < SCAN_PASS; ++q) {
+      const MotifRec mr = mrec[r0 + (q < np ? q : 0)];
+      wmask[q] = mr.w >= 64 ? ~0ull : ((1ull << mr.w) - 1ull);
+      nch[q] = mr.nch;
+      tf[q] = tab + mr.off;
+      v.begin(q, r0 + (q < np ? q : 0));
+      wmin = q < np && mr.w < wmin ? mr.w : wmin;
+    }
+    // (a window past the sequence's end has invalid bits: the passes' wider motifs need no bound of their own)
+    const uint32_t nwin = L >= (uint32_t)wmin ? L - (uint32_t)wmin + 1u : 0u;
+    // look-ahead buffer: bases s .. s+63 of the sequence (b0 low), their validity bits in vb
+    const uint64_t x0 = ldw(0), x1 = ldw(1);
+    uint32_t b0 = (uint32_t)x0, b1 = (uint32_t)(x0 >> 32), b2 = (uint32_t)x1, b3 = (uint32_t)(x1 >> 32);
+    uint64_t vb = (uint64_t)ldv(0) | ((uint64_t)ldv(1) << 32);
+    for (uint32_t s = 0, j = 2; s < nwin; ++j) {
+      uint64_t fw = ldw(j);
+      uint32_t fv = ldv(j);
+      const uint32_t cnt = nwin - s < 32u ? nwin - s : 32u;
+      for (uint32_t k = 0; k < cnt; ++k) {
+#pragma unroll
+        for (int q = 0; q < SCAN_PASS; ++q) {
+          if (q < np && (vb & wmask[q]) == wmask[q]) {
+            int32_t sf = 0, sr = 0;
+#pragma unroll
+            for (int c = 0; c < MAX_CHUNKS; ++c) {
+              if (c < nch[q]) {
+                const uint32_t idx = byte_of(b0, b1, b2, b3, c);
+                sf += tf[q][c * 256 + idx];
+                if (BOTH) sr += tf[q][(nch[q] + c) * 256 + idx];
+              }
+            }
+            v.window(q, s + k, sf, sr);
+          }
+        }
+        b0 = __builtin_amdgcn_alignbit(b1, b0, 2);
+        b1 = __builtin_amdgcn_alignbit(b2, b1, 2);
+        b2 = __builtin_amdgcn_alignbit(b3, b2, 2);
+        b3 = __builtin_amdgcn_alignbit((uint32_t)fw, b3, 2);
+        fw >>= 2;
+        vb = (vb >> 1) | ((uint64_t)(fv & 1u) << 63);
+        fv >>= 1;
+      }
+      s += cnt;
+    }
+#pragma unroll
+    for (int q = 0; q < SCAN_PASS; ++q)
+      if (q < np) v.end(q, r0 + q);
+  }
+}
+
+// pengk_motif_scan: the best window score of every motif on every sequence
+template <bool BOTH>
+struct BestVisit {
+  const MotifRec* mrec;
+  int32_t* best_out;
+  uint64_t n_seq, i;
+  int best[SCAN_PASS];
+  __device__ __forceinline__ void begin(int q, int) { best[q] = PENGK_SCORE_SENTINEL; }
+  __device__ __forceinline__ void window(int q, uint32_t, int32_t sf, int32_t sr) { best[q] = max(best[q], BOTH ? max(sf, sr) : sf); }
+  __device__ __forceinline__ void end(int q, int r) { best_out[(uint64_t)mrec[r].m * n_seq + i] = best[q]; }
+};
+
 template <bool BOTH>
 __global__ __launch_bounds__(SCAN_THREADS) void motif_scan_kernel(const uint64_t* __restrict__ words,
                                                                   const uint32_t* __restrict__ valid,
@@ -69,72 +158,8 @@ __global__ __launch_bounds__(SCAN_THREADS) void motif_scan_kernel(const uint64_t
   for (uint64_t i = blockIdx.x * (uint64_t)SCAN_THREADS + threadIdx.x; i < n_seq; i += (uint64_t)gridDim.x * SCAN_THREADS) {
     const uint32_t L = lens[i];
     const uint64_t w0 = (uint64_t)offs[i] >> 5;
-    const uint64_t* wp = words + w0;
-    const uint32_t* vp = valid ? valid + w0 : nullptr;
-    const uint32_t nw = (L + 31u) >> 5;
-    auto ldw = [&](uint32_t j) -> uint64_t { return j < nw ? wp[j] : 0ull; };
-    auto ldv = [&](uint32_t j) -> uint32_t {
-      if (j >= nw) return 0u;
-      if (vp) return vp[j];
-      const uint32_t rem = L - 32u * j;
-      return rem >= 32u ? 0xFFFFFFFFu : ((1u << rem) - 1u);
-    };
-    // SCAN_PASS motifs per pass over the sequence: the buffer's upkeep per base is shared by them
-    for (int r0 = 0; r0 < g.m1 - g.m0; r0 += SCAN_PASS) {
-      const int np = g.m1 - g.m0 - r0 < SCAN_PASS ? g.m1 - g.m0 - r0 : SCAN_PASS;
-      uint64_t wmask[SCAN_PASS];
-      int nch[SCAN_PASS], best[SCAN_PASS];
-      const int32_t* tf[SCAN_PASS];
-      int wmin = PENGK_MAX_MOTIF_LEN;
-#pragma unroll
-      for (int q = 0; q < SCAN_PASS; ++q) {
-        const MotifRec mr = mrec[r0 + (q < np ? q : 0)];
-        wmask[q] = mr.w >= 64 ? ~0ull : ((1ull << mr.w) - 1ull);
-        nch[q] = mr.nch;
-        tf[q] = tab + mr.off;
-        best[q] = PENGK_SCORE_SENTINEL;
-        wmin = q < np && mr.w < wmin ? mr.w : wmin;
-      }
-      // (a window past the sequence's end has invalid bits: the passes' wider motifs need no bound of their own)
-      const uint32_t nwin = L >= (uint32_t)wmin ? L - (uint32_t)wmin + 1u : 0u;
-      // look-ahead buffer: bases s .. s+63 of the sequence (b0 low), their validity bits in vb
-      const uint64_t x0 = ldw(0), x1 = ldw(1);
-      uint32_t b0 = (uint32_t)x0, b1 = (uint32_t)(x0 >> 32), b2 = (uint32_t)x1, b3 = (uint32_t)(x1 >> 32);
-      uint64_t vb = (uint64_t)ldv(0) | ((uint64_t)ldv(1) << 32);
-      for (uint32_t s = 0, j = 2; s < nwin; ++j) {
-        uint64_t fw = ldw(j);
-        uint32_t fv = ldv(j);
-        const uint32_t cnt = nwin - s < 32u ? nwin - s : 32u;
-        for (uint32_t k = 0; k < cnt; ++k) {
-#pragma unroll
-          for (int q = 0; q < SCAN_PASS; ++q) {
-            if (q < np && (vb & wmask[q]) == wmask[q]) {
-              int32_t sf = 0, sr = 0;
-#pragma unroll
-              for (int c = 0; c < MAX_CHUNKS; ++c) {
-                if (c < nch[q]) {
-                  const uint32_t idx = byte_of(b0, b1, b2, b3, c);
-                  sf += tf[q][c * 256 + idx];
-                  if (BOTH) sr += tf[q][(nch[q] + c) * 256 + idx];
-                }
-              }
-              best[q] = max(best[q], BOTH ? max(sf, sr) : sf);
-            }
-          }
-          b0 = __builtin_amdgcn_alignbit(b1, b0, 2);
-          b1 = __builtin_amdgcn_alignbit(b2, b1, 2);
-          b2 = __builtin_amdgcn_alignbit(b3, b2, 2);
-          b3 = __builtin_amdgcn_alignbit((uint32_t)fw, b3, 2);
-          fw >>= 2;
-          vb = (vb >> 1) | ((uint64_t)(fv & 1u) << 63);
-          fv >>= 1;
-        }
-        s += cnt;
-      }
-#pragma unroll
-      for (int q = 0; q < SCAN_PASS; ++q)
-        if (q < np) best_out[(uint64_t)mrec[r0 + q].m * n_seq + i] = best[q];
-    }
+    BestVisit<BOTH> v{mrec, best_out, n_seq, i, {}};
+    walk_sequence<BOTH>(words + w0, valid ? valid + w0 : nullptr, L, tab, mrec, g.m1 - g.m0, v);
   }
 }
 
@@ -231,10 +256,301 @@ __global__ __launch_bounds__(HIST_THREADS) void score_hist_kernel(const int32_t*
   }
 }
 
+// ---- motif sites (pengk_sites_*): every window strand at or above a motif's threshold, in a fixed order --------------
+constexpr int SITES_THREADS = 256;
+constexpr uint32_t SITES_BLOCK = PENGK_SITES_BLOCK;  // sequences per block total of pengk_sites_slices
+constexpr int XS_PER = 8;                            // offsets scan: elements per thread ...
+constexpr int XS_TILE = SITES_THREADS * XS_PER;      // ... and per workgroup
+
+// sites of every motif on every sequence: counts[m * n_seq + i] (uint64: 2 per window of a 2^32-base sequence)
+template <bool BOTH>
+struct CountVisit {
+  const MotifRec* mrec;
+  const int32_t* thr;  // by group record
+  unsigned long long* counts;
+  uint64_t n_seq, i;
+  int32_t t[SCAN_PASS];
+  unsigned long long c[SCAN_PASS];
+  __device__ __forceinline__ void begin(int q, int r) {
+    t[q] = thr[r];
+    c[q] = 0;
+  }
+  __device__ __forceinline__ void window(int q, uint32_t, int32_t sf, int32_t sr) {
+    c[q] += (unsigned)(sf >= t[q]) + (unsigned)(BOTH && sr >= t[q]);
+  }
+  __device__ __forceinline__ void end(int q, int r) { counts[(uint64_t)mrec[r].m * n_seq + i] = c[q]; }
+};
+
+// the records of sequences [i0, i1): sequence i's sites of motif m from d_so[m * (i1 - i0) + i - i0] on, in window order,
+// + before -; a record at or beyond cap is not written (the caller sized cap from the counts: none is)
+template <bool BOTH>
+struct EmitVisit {
+  const MotifRec* mrec;
+  const int32_t* thr;
+  const unsigned long long* so;
+  pengk_site* out;
+  uint64_t cap, ns, i, il;
+  int32_t t[SCAN_PASS];
+  uint64_t o[SCAN_PASS];
+  uint32_t ms[SCAN_PASS];
+  __device__ __forceinline__ void begin(int q, int r) {
+    t[q] = thr[r];
+    o[q] = so[(uint64_t)mrec[r].m * ns + il];
+    ms[q] = (uint32_t)mrec[r].m << 1;
+  }
+  __device__ __forceinline__ void put(int q, uint32_t pos, int32_t sc, uint32_t strand) {
+    if (o[q] < cap) {
+      pengk_site rec;
+      rec.seq = (uint32_t)il;
+      rec.pos = pos;
+      rec.score = sc;
+      rec.motif_strand = ms[q] | strand;
+      out[o[q]] = rec;
+    }
+    ++o[q];
+  }
+  __device__ __forceinline__ void window(int q, uint32_t pos, int32_t sf, int32_t sr) {
+    if (sf >= t[q]) put(q, pos, sf, 0u);
+    if (BOTH && sr >= t[q]) put(q, pos, sr, 1u);
+  }
+  __device__ __forceinline__ void end(int, int) {}
+};
+
+// one kernel for both passes: the shared walk, the visitor's state per sequence
+template <bool BOTH, bool EMIT>
+__global__ __launch_bounds__(SCAN_THREADS) void motif_sites_kernel(const uint64_t* __restrict__ words,
+                                                                   const uint32_t* __restrict__ valid,
+                                                                   const int64_t* __restrict__ offs,
+                                                                   const uint32_t* __restrict__ lens, uint64_t i0, uint64_t i1,
+                                                                   uint64_t n_seq, const int32_t* __restrict__ tables,
+                                                                   const MotifRec* __restrict__ recs,
+                                                                   const GroupRec* __restrict__ groups,
+                                                                   const int32_t* __restrict__ thr,
+                                                                   unsigned long long* __restrict__ counts,
+                                                                   const unsigned long long* __restrict__ so,
+                                                                   pengk_site* __restrict__ out, uint64_t cap) {
+  __shared__ int32_t tab[SCAN_TABLES * 256];
+  __shared__ MotifRec mrec[SCAN_MAX_MOTIFS];
+  __shared__ int32_t mthr[SCAN_MAX_MOTIFS];
+  const GroupRec g = groups[blockIdx.y];
+  for (int t = threadIdx.x; t < g.n_ints; t += SCAN_THREADS) tab[t] = tables[g.table0 + t];
+  for (int t = threadIdx.x; t < g.m1 - g.m0; t += SCAN_THREADS) {
+    mrec[t] = recs[g.m0 + t];
+    mthr[t] = thr[recs[g.m0 + t].m];
+  }
+  __syncthreads();
+  for (uint64_t i = i0 + blockIdx.x * (uint64_t)SCAN_THREADS + threadIdx.x; i < i1; i += (uint64_t)gridDim.x * SCAN_THREADS) {
+    const uint32_t L = lens[i];
+    const uint64_t w0 = (uint64_t)offs[i] >> 5;
+    if (EMIT) {
+      EmitVisit<BOTH> v{mrec, mthr, so, out, cap, i1 - i0, i, i - i0, {}, {}, {}};
+      walk_sequence<BOTH>(words + w0, valid ? valid + w0 : nullptr, L, tab, mrec, g.m1 - g.m0, v);
+    } else {
+      CountVisit<BOTH> v{mrec, mthr, counts, n_seq, i, {}, {}};
+      walk_sequence<BOTH>(words + w0, valid ? valid + w0 : nullptr, L, tab, mrec, g.m1 - g.m0, v);
+    }
+  }
+}
+
+// inclusive sum over the workgroup (sh: SITES_THREADS entries; every thread calls it)
+__device__ __forceinline__ unsigned long long block_inclusive_sum(unsigned long long v, unsigned long long* sh,
+                                                                  unsigned long long* total = nullptr) {
+  const int t = threadIdx.x;
+  sh[t] = v;
+  __syncthreads();
+  for (int d = 1; d < SITES_THREADS; d <<= 1) {
+    const unsigned long long x = t >= d ? sh[t - d] : 0ull;
+    __syncthreads();
+    sh[t] += x;
+    __syncthreads();
+  }
+  const unsigned long long r = sh[t];
+  if (total) *total = sh[SITES_THREADS - 1];
+  __syncthreads();
+  return r;
+}
+
+// per-sequence totals over the motifs, per-block totals (SITES_BLOCK sequences) and per-motif totals (added to mtot)
+__global__ __launch_bounds__(SITES_THREADS) void site_totals_kernel(const unsigned long long* __restrict__ counts, uint64_t n_seq,
+                                                                   int n_motifs, unsigned long long* __restrict__ seq_tot,
+                                                                   unsigned long long* __restrict__ block_tot,
+                                                                   unsigned long long* __restrict__ mtot) {
+  __shared__ unsigned long long sh[SITES_THREADS];
+  constexpr int PER = SITES_BLOCK / SITES_THREADS;
+  const uint64_t base = (uint64_t)blockIdx.x * SITES_BLOCK;
+  unsigned long long st[PER];
+#pragma unroll
+  for (int r = 0; r < PER; ++r) st[r] = 0;
+  for (int m = 0; m < n_motifs; ++m) {
+    unsigned long long ms = 0;
+#pragma unroll
+    for (int r = 0; r < PER; ++r) {
+      const uint64_t i = base + (uint64_t)r * SITES_THREADS + threadIdx.x;
+      if (i < n_seq) {
+        const unsigned long long c = counts[(uint64_t)m * n_seq + i];
+        st[r] += c;
+        ms += c;
+      }
+    }
+    ms = block_inclusive_sum(ms, sh);
+    if (threadIdx.x == SITES_THREADS - 1 && ms) atomicAdd(&mtot[m], ms);
+  }
+  unsigned long long bs = 0;
+#pragma unroll
+  for (int r = 0; r < PER; ++r) {
+    const uint64_t i = base + (uint64_t)r * SITES_THREADS + threadIdx.x;
+    if (i < n_seq) seq_tot[i] = st[r];
+    bs += st[r];
+  }
+  bs = block_inclusive_sum(bs, sh);
+  if (threadIdx.x == SITES_THREADS - 1) block_tot[blockIdx.x] = bs;
+}
+
+// exclusive scan of the counts of sequences [i0, i0 + ns), motif-major: element k = counts[(k / ns) * n_seq + i0 + k % ns]
+__device__ __forceinline__ unsigned long long xs_elem(const unsigned long long* counts, uint64_t n_seq, uint64_t i0, uint64_t ns,
+                                                      uint64_t k) {
+  return counts[(k / ns) * n_seq + i0 + k % ns];
+}
+
+__global__ __launch_bounds__(SITES_THREADS) void xscan_tiles_kernel(const unsigned long long* __restrict__ counts, uint64_t n_seq,
+                                                                    uint64_t i0, uint64_t ns, uint64_t n,
+                                                                    unsigned long long* __restrict__ part) {
+  __shared__ unsigned long long sh[SITES_THREADS];
+  const uint64_t k0 = (uint64_t)blockIdx.x * XS_TILE + (uint64_t)threadIdx.x * XS_PER;
+  unsigned long long s = 0;
+  for (int r = 0; r < XS_PER; ++r)
+    if (k0 + r < n) s += xs_elem(counts, n_seq, i0, ns, k0 + r);
+  s = block_inclusive_sum(s, sh);
+  if (threadIdx.x == SITES_THREADS - 1) part[blockIdx.x] = s;
+}
+
+// (one workgroup) the tiles' sums -> their exclusive prefix sums, in place
+__global__ __launch_bounds__(SITES_THREADS) void xscan_parts_kernel(unsigned long long* __restrict__ part, uint64_t n_tiles) {
+  __shared__ unsigned long long sh[SITES_THREADS];
+  unsigned long long carry = 0;
+  for (uint64_t b = 0; b < n_tiles; b += XS_TILE) {
+    unsigned long long v[XS_PER], s = 0;
+    const uint64_t k0 = b + (uint64_t)threadIdx.x * XS_PER;
+    for (int r = 0; r < XS_PER; ++r) {
+      v[r] = k0 + r < n_tiles ? part[k0 + r] : 0ull;
+      s += v[r];
+    }
+    unsigned long long tot = 0;
+    unsigned long long e = carry + block_inclusive_sum(s, sh, &tot) - s;
+    for (int r = 0; r < XS_PER; ++r) {
+      if (k0 + r < n_tiles) part[k0 + r] = e;
+      e += v[r];
+    }
+    carry += tot;
+  }
+}
+
+__global__ __launch_bounds__(SITES_THREADS) void xscan_apply_kernel(const unsigned long long* __restrict__ counts, uint64_t n_seq,
+                                                                    uint64_t i0, uint64_t ns, uint64_t n,
+                                                                    const unsigned long long* __restrict__ part,
+                                                                    unsigned long long* __restrict__ out) {
+  __shared__ unsigned long long sh[SITES_THREADS];
+  const uint64_t k0 = (uint64_t)blockIdx.x * XS_TILE + (uint64_t)threadIdx.x * XS_PER;
+  unsigned long long v[XS_PER], s = 0;
+  for (int r = 0; r < XS_PER; ++r) {
+    v[r] = k0 + r < n ? xs_elem(counts, n_seq, i0, ns, k0 + r) : 0ull;
+    s += v[r];
+  }
+  unsigned long long e = part[blockIdx.x] + block_inclusive_sum(s, sh) - s;
+  for (int r = 0; r < XS_PER; ++r) {
+    if (k0 + r < n) out[k0 + r] = e;
+    e += v[r];
+  }
+}
+
 int grid_for(pengk_ctx* ctx, uint64_t work, uint32_t per_block, uint32_t per_cu) {
   const uint64_t need = (work + per_block - 1) / per_block;
   const uint64_t cap = (uint64_t)ctx->num_cu * per_cu;
   return (int)std::max<uint64_t>(1, std::min(need, cap));
+}
+
+}  // namespace
+}  // namespace pengk
+
+namespace pengk {
+namespace {
+
+int check_motifs(const char* who, int n_motifs, const int32_t* h_S, const int32_t* h_len) {
+  for (int m = 0; m < n_motifs; ++m) {
+    if (h_len[m] < 1 || h_len[m] > PENGK_MAX_MOTIF_LEN)
+      return fail(PENGK_ERR_ARG, "%s: motif %d has width %d (1..%d)", who, m, h_len[m], PENGK_MAX_MOTIF_LEN);
+    for (int j = 0; j < h_len[m] * 4; ++j) {
+      const int32_t v = h_S[(size_t)m * PENGK_MAX_MOTIF_LEN * 4 + j];
+      if (v < -2000 || v > 2000) return fail(PENGK_ERR_ARG, "%s: motif %d: log-odds %d outside [-2000, 2000]", who, m, v);
+    }
+  }
+  return PENGK_OK;
+}
+
+struct StagedMotifs {
+  const int32_t* tables = nullptr;
+  const MotifRec* recs = nullptr;
+  const GroupRec* groups = nullptr;
+  const int32_t* thr = nullptr;  // (h_thr given: n_motifs thresholds, by motif index)
+  int n_groups = 0;
+};
+
+// chunk tables, motif records and groups (greedy, in motif order) -- and h_thr when given -- staged in ctx->d_score
+int stage_motifs(pengk_ctx* ctx, int n_motifs, const int32_t* h_S, const int32_t* h_len, int strands, const int32_t* h_thr,
+                 StagedMotifs* out) {
+  std::vector<int32_t> tables;
+  std::vector<MotifRec> recs;
+  std::vector<GroupRec> groups;
+  for (int m = 0; m < n_motifs; ++m) {
+    const int w = h_len[m], nch = (w + 3) / 4;
+    const int need = nch * strands * 256;
+    if (groups.empty() || groups.back().n_ints + need > SCAN_TABLES * 256) {
+      GroupRec g;
+      g.m0 = g.m1 = (int32_t)recs.size();
+      g.table0 = (int32_t)tables.size();
+      g.n_ints = 0;
+      groups.push_back(g);
+    }
+    GroupRec& g = groups.back();
+    MotifRec r;
+    r.off = g.n_ints;
+    r.w = w;
+    r.nch = nch;
+    r.m = m;
+    recs.push_back(r);
+    g.m1 = (int32_t)recs.size();
+    g.n_ints += need;
+    const int32_t* S = h_S + (size_t)m * PENGK_MAX_MOTIF_LEN * 4;
+    for (int st = 0; st < strands; ++st)
+      for (int c = 0; c < nch; ++c)
+        for (int idx = 0; idx < 256; ++idx) {
+          int32_t v = 0;
+          for (int k = 0; k < 4 && 4 * c + k < w; ++k) {
+            const int j = 4 * c + k, a = (idx >> (2 * k)) & 3;
+            v += st == 0 ? S[j * 4 + a] : S[(w - 1 - j) * 4 + (3 - a)];  // reverse complement: S_rc[j][a] = S[w-1-j][3-a]
+          }
+          tables.push_back(v);
+        }
+  }
+  const size_t tb = tables.size() * sizeof(int32_t), rb = recs.size() * sizeof(MotifRec), gb = groups.size() * sizeof(GroupRec);
+  const size_t hb = h_thr ? (size_t)n_motifs * sizeof(int32_t) : 0;
+  int rc = ensure_scratch(ctx, &ctx->d_score, &ctx->score_bytes, tb + rb + gb + hb);
+  if (rc) return rc;
+  char* base = (char*)ctx->d_score;
+  std::vector<char> staged(tb + rb + gb + hb);
+  memcpy(staged.data(), tables.data(), tb);
+  memcpy(staged.data() + tb, recs.data(), rb);
+  memcpy(staged.data() + tb + rb, groups.data(), gb);
+  if (hb) memcpy(staged.data() + tb + rb + gb, h_thr, hb);
+  // (synchronous: the staging vector dies with this call, and the scratch may still be read by an earlier scan)
+  PENGK_HIP(hipStreamSynchronize(ctx->stream));
+  PENGK_HIP(hipMemcpy(base, staged.data(), staged.size(), hipMemcpyHostToDevice));
+  out->tables = (const int32_t*)base;
+  out->recs = (const MotifRec*)(base + tb);
+  out->groups = (const GroupRec*)(base + tb + rb);
+  out->thr = hb ? (const int32_t*)(base + tb + rb + gb) : nullptr;
+  out->n_groups = (int)groups.size();
+  return PENGK_OK;
 }
 
 }  // namespace
@@ -325,73 +641,20 @@ int pengk_motif_scan(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_
                      int both_strands, int32_t* d_best) {
   if (!ctx || n_motifs < 0 || (n_motifs && (!h_S || !h_len)) || (n_seq && n_motifs && (!d_words || !d_offs || !d_lens || !d_best)))
     return fail(PENGK_ERR_ARG, "pengk_motif_scan: bad argument");
-  for (int m = 0; m < n_motifs; ++m) {
-    if (h_len[m] < 1 || h_len[m] > PENGK_MAX_MOTIF_LEN)
-      return fail(PENGK_ERR_ARG, "pengk_motif_scan: motif %d has width %d (1..%d)", m, h_len[m], PENGK_MAX_MOTIF_LEN);
-    for (int j = 0; j < h_len[m] * 4; ++j) {
-      const int32_t v = h_S[(size_t)m * PENGK_MAX_MOTIF_LEN * 4 + j];
-      if (v < -2000 || v > 2000) return fail(PENGK_ERR_ARG, "pengk_motif_scan: motif %d: log-odds %d outside [-2000, 2000]", m, v);
-    }
-  }
+  int rc = check_motifs("pengk_motif_scan", n_motifs, h_S, h_len);
+  if (rc) return rc;
   SCORE_ENTER(ctx);
   if (n_seq == 0 || n_motifs == 0) return PENGK_OK;
-  const int strands = both_strands ? 2 : 1;
-  // chunk tables, motif records and groups (greedy, in motif order)
-  std::vector<int32_t> tables;
-  std::vector<MotifRec> recs;
-  std::vector<GroupRec> groups;
-  for (int m = 0; m < n_motifs; ++m) {
-    const int w = h_len[m], nch = (w + 3) / 4;
-    const int need = nch * strands * 256;
-    if (groups.empty() || groups.back().n_ints + need > SCAN_TABLES * 256) {
-      GroupRec g;
-      g.m0 = g.m1 = (int32_t)recs.size();
-      g.table0 = (int32_t)tables.size();
-      g.n_ints = 0;
-      groups.push_back(g);
-    }
-    GroupRec& g = groups.back();
-    MotifRec r;
-    r.off = g.n_ints;
-    r.w = w;
-    r.nch = nch;
-    r.m = m;
-    recs.push_back(r);
-    g.m1 = (int32_t)recs.size();
-    g.n_ints += need;
-    const int32_t* S = h_S + (size_t)m * PENGK_MAX_MOTIF_LEN * 4;
-    for (int st = 0; st < strands; ++st)
-      for (int c = 0; c < nch; ++c)
-        for (int idx = 0; idx < 256; ++idx) {
-          int32_t v = 0;
-          for (int k = 0; k < 4 && 4 * c + k < w; ++k) {
-            const int j = 4 * c + k, a = (idx >> (2 * k)) & 3;
-            v += st == 0 ? S[j * 4 + a] : S[(w - 1 - j) * 4 + (3 - a)];  // reverse complement: S_rc[j][a] = S[w-1-j][3-a]
-          }
-          tables.push_back(v);
-        }
-  }
-  const size_t tb = tables.size() * sizeof(int32_t), rb = recs.size() * sizeof(MotifRec), gb = groups.size() * sizeof(GroupRec);
-  int rc = ensure_scratch(ctx, &ctx->d_score, &ctx->score_bytes, tb + rb + gb);
+  StagedMotifs st;
+  rc = stage_motifs(ctx, n_motifs, h_S, h_len, both_strands ? 2 : 1, nullptr, &st);
   if (rc) return rc;
-  char* base = (char*)ctx->d_score;
-  std::vector<char> staged(tb + rb + gb);
-  memcpy(staged.data(), tables.data(), tb);
-  memcpy(staged.data() + tb, recs.data(), rb);
-  memcpy(staged.data() + tb + rb, groups.data(), gb);
-  // (synchronous: the staging vector dies with this call, and the scratch may still be read by an earlier scan)
-  PENGK_HIP(hipStreamSynchronize(ctx->stream));
-  PENGK_HIP(hipMemcpy(base, staged.data(), staged.size(), hipMemcpyHostToDevice));
-  const dim3 grid(grid_for(ctx, n_seq, SCAN_THREADS, 8), (unsigned)groups.size());
-  const int32_t* dt = (const int32_t*)base;
-  const MotifRec* dr = (const MotifRec*)(base + tb);
-  const GroupRec* dg = (const GroupRec*)(base + tb + rb);
+  const dim3 grid(grid_for(ctx, n_seq, SCAN_THREADS, 8), (unsigned)st.n_groups);
   if (both_strands)
     hipLaunchKernelGGL(motif_scan_kernel<true>, grid, dim3(SCAN_THREADS), 0, ctx->stream, d_words, d_valid, d_offs, d_lens, n_seq,
-                       dt, dr, dg, d_best);
+                       st.tables, st.recs, st.groups, d_best);
   else
     hipLaunchKernelGGL(motif_scan_kernel<false>, grid, dim3(SCAN_THREADS), 0, ctx->stream, d_words, d_valid, d_offs, d_lens, n_seq,
-                       dt, dr, dg, d_best);
+                       st.tables, st.recs, st.groups, d_best);
   PENGK_HIP(hipGetLastError());
   return PENGK_OK;
 }
@@ -465,6 +728,197 @@ int pengk_score_summary(const uint64_t* h_pos, const uint64_t* h_neg, uint64_t n
   const double fpr = (double)neg_ge / (double)nneg, tpr = (double)pos_ge / (double)npos;
   double occ = fpr == 1.0 ? 0.0 : (tpr - fpr) / (1.0 - fpr);
   *occur_out = occ < 0.0 ? 0.0 : occ > 1.0 ? 1.0 : occ;
+  return PENGK_OK;
+}
+
+int pengk_score_tail_pvalues(const int32_t* h_S, int w, const float* h_bg, int32_t* lo_out, int32_t* hi_out, double* h_tail) {
+  if (!h_S || !h_bg || !lo_out || !hi_out || w < 1 || w > PENGK_MAX_MOTIF_LEN)
+    return fail(PENGK_ERR_ARG, "pengk_score_tail_pvalues: bad argument");
+  int32_t lo = 0, hi = 0;
+  for (int j = 0; j < w; ++j) {
+    int32_t mn = 2000, mx = -2000;
+    for (int a = 0; a < 4; ++a) {
+      const int32_t v = h_S[j * 4 + a];
+      if (v < -2000 || v > 2000) return fail(PENGK_ERR_ARG, "pengk_score_tail_pvalues: log-odds %d outside [-2000, 2000]", v);
+      mn = std::min(mn, v);
+      mx = std::max(mx, v);
+    }
+    lo += mn;
+    hi += mx;
+  }
+  *lo_out = lo;
+  *hi_out = hi;
+  if (!h_tail) return PENGK_OK;
+  double bg[4];
+  for (int a = 0; a < 4; ++a) bg[a] = (double)h_bg[a];
+  // q_j over the scores [clo, chi] of the first j columns; q_{j+1}[t] = sum over a = 0..3, in this order, of
+  // q_j[t - S[j][a]] * bg[a], each from 0.0
+  const size_t n = (size_t)(hi - lo) + 1;
+  std::vector<double> q(n, 0.0), nq(n, 0.0);
+  q[0] = 1.0;
+  int32_t clo = 0, chi = 0;
+  for (int j = 0; j < w; ++j) {
+    int32_t mn = 2000, mx = -2000;
+    for (int a = 0; a < 4; ++a) {
+      mn = std::min(mn, h_S[j * 4 + a]);
+      mx = std::max(mx, h_S[j * 4 + a]);
+    }
+    const int32_t nlo = clo + mn, nhi = chi + mx;
+    for (int32_t t = nlo; t <= nhi; ++t) {
+      double v = 0.0;
+      for (int a = 0; a < 4; ++a) {
+        const int32_t u = t - h_S[j * 4 + a];
+        if (u >= clo && u <= chi) v += q[(size_t)(u - clo)] * bg[a];
+      }
+      nq[(size_t)(t - nlo)] = v;
+    }
+    q.swap(nq);
+    clo = nlo;
+    chi = nhi;
+  }
+  // the tail, summed from the highest score down
+  double acc = 0.0;
+  for (int64_t t = hi; t >= lo; --t) {
+    acc += q[(size_t)(t - lo)];
+    h_tail[t - lo] = acc;
+  }
+  return PENGK_OK;
+}
+
+int pengk_score_threshold(const double* h_tail, int32_t lo, int32_t hi, double p, int32_t* t_out) {
+  if (!h_tail || !t_out || hi < lo || !(p > 0.0 && p <= 1.0)) return fail(PENGK_ERR_ARG, "pengk_score_threshold: bad argument");
+  int32_t t = lo;
+  while (t <= hi && !(h_tail[t - lo] <= p)) ++t;
+  *t_out = t;
+  return PENGK_OK;
+}
+
+int pengk_sites_count(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_valid, const int64_t* d_offs,
+                      const uint32_t* d_lens, uint64_t n_seq, int n_motifs, const int32_t* h_S, const int32_t* h_len,
+                      int both_strands, const int32_t* h_thr, uint64_t* d_counts) {
+  if (!ctx || n_motifs < 0 || (n_motifs && (!h_S || !h_len || !h_thr)) ||
+      (n_seq && n_motifs && (!d_words || !d_offs || !d_lens || !d_counts)))
+    return fail(PENGK_ERR_ARG, "pengk_sites_count: bad argument");
+  int rc = check_motifs("pengk_sites_count", n_motifs, h_S, h_len);
+  if (rc) return rc;
+  SCORE_ENTER(ctx);
+  if (n_seq == 0 || n_motifs == 0) return PENGK_OK;
+  StagedMotifs st;
+  rc = stage_motifs(ctx, n_motifs, h_S, h_len, both_strands ? 2 : 1, h_thr, &st);
+  if (rc) return rc;
+  const dim3 grid(grid_for(ctx, n_seq, SCAN_THREADS, 8), (unsigned)st.n_groups);
+  unsigned long long* c = (unsigned long long*)d_counts;
+  if (both_strands)
+    hipLaunchKernelGGL((motif_sites_kernel<true, false>), grid, dim3(SCAN_THREADS), 0, ctx->stream, d_words, d_valid, d_offs, d_lens,
+                       (uint64_t)0, n_seq, n_seq, st.tables, st.recs, st.groups, st.thr, c, nullptr, nullptr, (uint64_t)0);
+  else
+    hipLaunchKernelGGL((motif_sites_kernel<false, false>), grid, dim3(SCAN_THREADS), 0, ctx->stream, d_words, d_valid, d_offs, d_lens,
+                       (uint64_t)0, n_seq, n_seq, st.tables, st.recs, st.groups, st.thr, c, nullptr, nullptr, (uint64_t)0);
+  PENGK_HIP(hipGetLastError());
+  return PENGK_OK;
+}
+
+int pengk_sites_slices(pengk_ctx* ctx, const uint64_t* d_counts, uint64_t n_seq, int n_motifs, uint64_t* h_motif_totals,
+                       uint64_t max_slices, uint64_t* h_bounds, uint64_t* h_records, uint64_t* n_slices) {
+  if (!ctx || n_motifs < 0 || !n_slices || (n_motifs && !h_motif_totals) || (max_slices && (!h_bounds || !h_records)) ||
+      (n_seq && n_motifs && !d_counts))
+    return fail(PENGK_ERR_ARG, "pengk_sites_slices: bad argument");
+  SCORE_ENTER(ctx);
+  *n_slices = 0;
+  for (int m = 0; m < n_motifs; ++m) h_motif_totals[m] = 0;
+  if (n_seq == 0) return PENGK_OK;
+  const uint64_t nb = (n_seq + SITES_BLOCK - 1) / SITES_BLOCK;
+  std::vector<uint64_t> bt(nb, 0);
+  unsigned long long *seq_tot = nullptr, *block_tot = nullptr;
+  if (n_motifs) {
+    const size_t bytes = (n_seq + nb + (size_t)n_motifs) * sizeof(uint64_t);
+    int rc = ensure_scratch(ctx, &ctx->d_sites, &ctx->sites_bytes, bytes);
+    if (rc) return rc;
+    seq_tot = (unsigned long long*)ctx->d_sites;
+    block_tot = seq_tot + n_seq;
+    unsigned long long* mtot = block_tot + nb;
+    PENGK_HIP(hipMemsetAsync(mtot, 0, (size_t)n_motifs * sizeof(uint64_t), ctx->stream));
+    hipLaunchKernelGGL(site_totals_kernel, dim3((unsigned)nb), dim3(SITES_THREADS), 0, ctx->stream,
+                       (const unsigned long long*)d_counts, n_seq, n_motifs, seq_tot, block_tot, mtot);
+    PENGK_HIP(hipGetLastError());
+    PENGK_HIP(hipMemcpyAsync(bt.data(), block_tot, nb * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    PENGK_HIP(hipMemcpyAsync(h_motif_totals, mtot, (size_t)n_motifs * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    PENGK_HIP(hipStreamSynchronize(ctx->stream));
+  }
+  // slices of whole blocks while their records fit the budget; a block above it alone is cut between its sequences, and a
+  // sequence above it is a slice of its own
+  const uint64_t B = ctx->sites_record_budget;
+  const uint64_t MAX_SEQ = 1ull << 31;  // (a record's sequence is an index into its slice: uint32)
+  uint64_t ns = 0, i0 = 0, acc = 0;
+  auto close = [&](uint64_t i1) {
+    if (ns < max_slices) {
+      h_bounds[ns] = i0;
+      h_bounds[ns + 1] = i1;
+      h_records[ns] = acc;
+    }
+    ++ns;
+    i0 = i1;
+    acc = 0;
+  };
+  std::vector<uint64_t> st;
+  for (uint64_t b = 0; b < nb; ++b) {
+    const uint64_t bb = b * SITES_BLOCK, be = std::min<uint64_t>(n_seq, bb + SITES_BLOCK);
+    if (be - i0 > MAX_SEQ) close(bb);
+    if (acc + bt[b] <= B) {
+      acc += bt[b];
+      continue;
+    }
+    if (bt[b] <= B) {
+      close(bb);
+      acc = bt[b];
+      continue;
+    }
+    st.resize(be - bb);
+    PENGK_HIP(hipMemcpy(st.data(), seq_tot + bb, (be - bb) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    for (uint64_t i = bb; i < be; ++i) {
+      const uint64_t t = st[i - bb];
+      if (acc + t > B && i > i0) close(i);
+      acc += t;
+    }
+  }
+  close(n_seq);
+  *n_slices = ns;
+  return PENGK_OK;
+}
+
+int pengk_sites_emit(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_valid, const int64_t* d_offs,
+                     const uint32_t* d_lens, uint64_t n_seq, int n_motifs, const int32_t* h_S, const int32_t* h_len,
+                     int both_strands, const int32_t* h_thr, const uint64_t* d_counts, uint64_t i0, uint64_t i1,
+                     pengk_site* d_sites, uint64_t cap) {
+  if (!ctx || n_motifs < 0 || i0 > i1 || i1 > n_seq || i1 - i0 > (1ull << 31) || (n_motifs && (!h_S || !h_len || !h_thr)) ||
+      (i1 > i0 && n_motifs && (!d_words || !d_offs || !d_lens || !d_counts || (cap && !d_sites))))
+    return fail(PENGK_ERR_ARG, "pengk_sites_emit: bad argument");
+  int rc = check_motifs("pengk_sites_emit", n_motifs, h_S, h_len);
+  if (rc) return rc;
+  SCORE_ENTER(ctx);
+  if (i1 == i0 || n_motifs == 0) return PENGK_OK;
+  const uint64_t ns = i1 - i0, n = ns * (uint64_t)n_motifs, n_tiles = (n + XS_TILE - 1) / XS_TILE;
+  StagedMotifs st;
+  rc = stage_motifs(ctx, n_motifs, h_S, h_len, both_strands ? 2 : 1, h_thr, &st);
+  if (rc) return rc;
+  rc = ensure_scratch(ctx, &ctx->d_sites, &ctx->sites_bytes, (n + n_tiles) * sizeof(uint64_t));
+  if (rc) return rc;
+  unsigned long long* so = (unsigned long long*)ctx->d_sites;
+  unsigned long long* part = so + n;
+  const unsigned long long* c = (const unsigned long long*)d_counts;
+  // where each (motif, sequence) writes: the exclusive scan of the counts, motif-major
+  hipLaunchKernelGGL(xscan_tiles_kernel, dim3((unsigned)n_tiles), dim3(SITES_THREADS), 0, ctx->stream, c, n_seq, i0, ns, n, part);
+  hipLaunchKernelGGL(xscan_parts_kernel, dim3(1), dim3(SITES_THREADS), 0, ctx->stream, part, n_tiles);
+  hipLaunchKernelGGL(xscan_apply_kernel, dim3((unsigned)n_tiles), dim3(SITES_THREADS), 0, ctx->stream, c, n_seq, i0, ns, n, part, so);
+  PENGK_HIP(hipGetLastError());
+  const dim3 grid(grid_for(ctx, ns, SCAN_THREADS, 8), (unsigned)st.n_groups);
+  if (both_strands)
+    hipLaunchKernelGGL((motif_sites_kernel<true, true>), grid, dim3(SCAN_THREADS), 0, ctx->stream, d_words, d_valid, d_offs, d_lens, i0,
+                       i1, n_seq, st.tables, st.recs, st.groups, st.thr, nullptr, so, d_sites, cap);
+  else
+    hipLaunchKernelGGL((motif_sites_kernel<false, true>), grid, dim3(SCAN_THREADS), 0, ctx->stream, d_words, d_valid, d_offs, d_lens, i0,
+                       i1, n_seq, st.tables, st.recs, st.groups, st.thr, nullptr, so, d_sites, cap);
+  PENGK_HIP(hipGetLastError());
   return PENGK_OK;
 }
 

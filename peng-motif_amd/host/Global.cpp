@@ -44,13 +44,15 @@ unsigned Global::minimum_processed_motifs = 0;
 int Global::maximum_optimized_patterns = 50;
 bool Global::scoreMotifs = false;
 unsigned long long Global::scoreSeed = 1;
+char* Global::sitesFilename = nullptr;
+double Global::sitesPvalue = 1e-4;
 
 void Global::init(int nargs, char* args[]) {
   readArguments(nargs, args);
   Alphabet::init(alphabetType);
   pengk_host::start_context();  // the device runtime starts while the FASTA files are read
   pengk_host::start_sharded_ingest();  // multi-GPU run: every rank reads its own byte range of the files
-  pengk_host::keep_host_codes(scoreMotifs);  // (the scoring scans the input after the motifs are found)
+  pengk_host::keep_host_codes(scoreMotifs || sitesFilename);  // (the scoring and the sites scan the input after the motifs are found)
   // both strands are handled inside the count; sequences are always read single stranded
   // ... and every chunk of the input set is packed and sent to the device while the rest is still being read
   pengk_host::begin_streaming_pack(patternLength);
@@ -192,6 +194,17 @@ void Global::readArguments(int nargs, char* args[]) {
       scoreMotifs = true;
     } else if (!strcmp(a, "--score-seed")) {
       scoreSeed = std::stoull(need(i, nargs, args, printHelp));
+    } else if (!strcmp(a, "--sites")) {
+      sitesFilename = (char*)need(i, nargs, args, printHelp);
+    } else if (!strcmp(a, "--sites-pvalue")) {
+      const char* v = need(i, nargs, args, printHelp);
+      char* end = nullptr;
+      sitesPvalue = std::strtod(v, &end);
+      if (end == v || *end || !(sitesPvalue > 0.0 && sitesPvalue <= 1.0)) {
+        printHelp();
+        log_line("ERROR", "--sites-pvalue must be a number in (0, 1]");
+        exit(4);
+      }
     } else if (!strcmp(a, "--version")) {
       std::cout << "peng_motif " << VERSION_NUMBER << std::endl;  // (src/Global.cpp:299-301: without the word)
       exit(0);
@@ -234,6 +247,9 @@ void Global::printHelp() {
   printf("  --score-motifs                 score every motif against as many sequences sampled from the background\n");
   printf("                                 model (zoops_score = AUC, occur) and rank the motifs by it\n");
   printf("  --score-seed INT               seed of the sampled sequences (default 1)\n");
+  printf("  --sites FILE                   write every occurrence of the motifs (TSV: sequence, position, strand,\n");
+  printf("                                 score, p-value) at p-value --sites-pvalue or below\n");
+  printf("  --sites-pvalue FLOAT           p-value threshold of --sites, in (0, 1] (default 1e-4)\n");
   printf("  --threads INT                  accepted for compatibility\n");
   printf("  --device INT                   HIP device index (default 0)\n");
   printf("  -v INT                         verbosity\n");

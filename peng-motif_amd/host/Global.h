@@ -59,6 +59,8 @@ class Global {
 
   static bool scoreMotifs;                   // --score-motifs (new: scripts/shoot_peng.py's scoring step, on the device)
   static unsigned long long scoreSeed;       // --score-seed
+  static char* sitesFilename;                // --sites (new: every motif occurrence with its p-value)
+  static double sitesPvalue;                 // --sites-pvalue
 
   static void init(int nargs, char* args[]);
   static void destruct();

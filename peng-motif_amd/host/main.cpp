@@ -2,6 +2,7 @@
 // and exit codes as the reference's src/main.cpp; the hot loops run on the GPU through libpengk.
 #include <algorithm>
 #include <chrono>
+#include <memory>
 #include <unistd.h>
 
 #include <cstdio>
@@ -13,6 +14,7 @@
 #include "device.h"
 #include "iupac_pattern.h"
 #include "motif_score.h"
+#include "motif_sites.h"
 #include "peng.h"
 
 namespace {
@@ -101,10 +103,16 @@ int main(int nargs, char** args) {
   clock.lap("process (count, sweep, hill-climb, PWMs, EM, merging)");
   peng.filter_redundancy(Global::mergeBitfactorThreshold, result);
   std::vector<MotifScore> scores;
+  // (the scoring and the sites share one scan layout of the input)
+  std::unique_ptr<ScanInput> scan;
+  if (Global::scoreMotifs || Global::sitesFilename) {
+    scan.reset(new ScanInput);
+    build_scan_input(*Global::inputSequenceSet, scan.get());
+  }
   if (Global::scoreMotifs) {
     // the writers' order first, then stable by zoops_score descending (scripts/shoot_peng.py re-ranks the motifs so)
     std::sort(result.begin(), result.end(), sort_IUPAC_patterns);
-    scores = score_motifs(result, *Global::inputSequenceSet, *bgModel, Global::bgModelOrder,
+    scores = score_motifs(result, *Global::inputSequenceSet, *scan, *bgModel, Global::bgModelOrder,
                           Global::strand == Strand::BOTH_STRANDS, Global::scoreSeed);
     std::vector<size_t> order(result.size());
     for (size_t i = 0; i < order.size(); ++i) order[i] = i;
@@ -120,6 +128,15 @@ int main(int nargs, char** args) {
     clock.lap("score");
   }
   const std::vector<MotifScore>* sc = Global::scoreMotifs ? &scores : nullptr;
+  if (Global::sitesFilename) {
+    // the MEME file's order: as it is, or as the writers sort it (the same sort of the same vector: the same order)
+    std::vector<IUPACPattern*> order(result);
+    if (!sc) std::sort(order.begin(), order.end(), sort_IUPAC_patterns);
+    write_motif_sites(order, *Global::inputSequenceSet, *scan, *bgModel, Global::strand == Strand::BOTH_STRANDS,
+                      Global::sitesPvalue, Global::sitesFilename);
+    clock.lap("sites");
+  }
+  scan.reset();
   if (pengk_host::rank() == 0) {
     if (Global::outputFilename) peng.printShortMeme(result, Global::outputFilename, bgModel, sc);
     if (Global::jsonFilename) peng.printJson(result, Global::jsonFilename, VERSION_NUMBER, bgModel, sc);

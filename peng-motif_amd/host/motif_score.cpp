@@ -14,15 +14,29 @@ int32_t log_odds(float p, float b) {
 }
 }  // namespace
 
-std::vector<MotifScore> score_motifs(const std::vector<IUPACPattern*>& pats, SequenceSet& set, BackgroundModel& bg, int K,
-                                     bool both_strands, uint64_t seed) {
-  using pengk_host::check;
-  using pengk_host::DeviceBuffer;
-  pengk_host::Lap lap("  score: ");
+void motif_log_odds(const std::vector<IUPACPattern*>& pats, const float* bg0, std::vector<int32_t>& S, std::vector<int32_t>& len,
+                    const char* who) {
   const int n_motifs = (int)pats.size();
-  std::vector<MotifScore> out(n_motifs);
+  S.assign((size_t)std::max(n_motifs, 1) * PENGK_MAX_MOTIF_LEN * 4, 0);
+  len.assign(std::max(n_motifs, 1), 0);
+  for (int m = 0; m < n_motifs; ++m) {
+    const int w = (int)pats[m]->get_pattern_length();
+    if (w > PENGK_MAX_MOTIF_LEN) {
+      std::cerr << "Error: " << who << ": motif width " << w << " above " << PENGK_MAX_MOTIF_LEN << std::endl;
+      exit(1);
+    }
+    len[m] = w;
+    float** pwm = pats[m]->get_pwm();
+    for (int j = 0; j < w; ++j)
+      for (int a = 0; a < 4; ++a) S[((size_t)m * PENGK_MAX_MOTIF_LEN + j) * 4 + a] = log_odds(pwm[j][a], bg0[a]);
+  }
+}
+
+void build_scan_input(SequenceSet& set, ScanInput* in) {
+  using pengk_host::check;
+  pengk_host::Lap lap("  scan layout: ");
   if (set.codesReleased()) {
-    std::cerr << "Error: motif scoring: the sequences are no longer held on the host" << std::endl;
+    std::cerr << "Error: motif scan: the sequences are no longer held on the host" << std::endl;
     exit(1);
   }
   // scan layout of this rank's records, chunk by chunk (the chunks' words are disjoint: built by several threads)
@@ -59,39 +73,41 @@ std::vector<MotifScore> score_motifs(const std::vector<IUPACPattern*>& pats, Seq
     for (auto& x : th) x.join();
     for (int r : rc) check(r, "pengk_scan_layout_build");
   }
-  lap("scan layout built");
-  DeviceBuffer<uint64_t> d_words(n_words), d_neg(n_words);
-  DeviceBuffer<uint32_t> d_valid(n_words), d_lens(lens.size());
-  DeviceBuffer<int64_t> d_offs(offs.size());
-  d_words.upload(words.data(), n_words);
-  d_valid.upload(valid.data(), n_words);
-  d_offs.upload(offs.data(), offs.size());
-  d_lens.upload(lens.data(), lens.size());
-  lap("scan layout uploaded");
+  lap("built");
+  in->n_local = n_local;
+  in->n_words = n_words;
+  in->d_words.resize(n_words);
+  in->d_valid.resize(n_words);
+  in->d_offs.resize(offs.size());
+  in->d_lens.resize(lens.size());
+  in->d_words.upload(words.data(), n_words);
+  in->d_valid.upload(valid.data(), n_words);
+  in->d_offs.upload(offs.data(), offs.size());
+  in->d_lens.upload(lens.data(), lens.size());
+  lap("uploaded");
+}
+
+std::vector<MotifScore> score_motifs(const std::vector<IUPACPattern*>& pats, SequenceSet& set, const ScanInput& in,
+                                     BackgroundModel& bg, int K, bool both_strands, uint64_t seed) {
+  using pengk_host::check;
+  using pengk_host::DeviceBuffer;
+  pengk_host::Lap lap("  score: ");
+  const int n_motifs = (int)pats.size();
+  std::vector<MotifScore> out(n_motifs);
+  const size_t n_local = in.n_local;
+  const uint64_t n_words = in.n_words;
+  DeviceBuffer<uint64_t> d_neg(n_words);
 
   // log-odds against the background letter frequencies, score ranges, histogram offsets
   const float* bg0 = bg.getV()[0];
-  std::vector<int32_t> S((size_t)std::max(n_motifs, 1) * PENGK_MAX_MOTIF_LEN * 4, 0), len(std::max(n_motifs, 1), 0),
-      lo(std::max(n_motifs, 1), 0), hi(std::max(n_motifs, 1), 0);
+  std::vector<int32_t> S, len, lo(std::max(n_motifs, 1), 0), hi(std::max(n_motifs, 1), 0);
+  motif_log_odds(pats, bg0, S, len, "motif scoring");
   std::vector<uint64_t> hoffs(n_motifs + 1, 0);
   for (int m = 0; m < n_motifs; ++m) {
-    const int w = (int)pats[m]->get_pattern_length();
-    if (w > PENGK_MAX_MOTIF_LEN) {
-      std::cerr << "Error: motif scoring: motif width " << w << " above " << PENGK_MAX_MOTIF_LEN << std::endl;
-      exit(1);
-    }
-    len[m] = w;
-    float** pwm = pats[m]->get_pwm();
-    for (int j = 0; j < w; ++j) {
-      int32_t mn = 2000, mx = -2000;
-      for (int a = 0; a < 4; ++a) {
-        const int32_t v = log_odds(pwm[j][a], bg0[a]);
-        S[((size_t)m * PENGK_MAX_MOTIF_LEN + j) * 4 + a] = v;
-        mn = std::min(mn, v);
-        mx = std::max(mx, v);
-      }
-      lo[m] += mn;
-      hi[m] += mx;
+    for (int j = 0; j < len[m]; ++j) {
+      const int32_t* r = &S[((size_t)m * PENGK_MAX_MOTIF_LEN + j) * 4];
+      lo[m] += std::min(std::min(r[0], r[1]), std::min(r[2], r[3]));
+      hi[m] += std::max(std::max(r[0], r[1]), std::max(r[2], r[3]));
     }
     hoffs[m + 1] = hoffs[m] + (uint64_t)(hi[m] - lo[m] + 2);
   }
@@ -113,14 +129,14 @@ std::vector<MotifScore> score_motifs(const std::vector<IUPACPattern*>& pats, Seq
   pengk_ctx* ctx = pengk_host::context();
   check(pengk_memset(ctx, d_hist.get(), 0, 2 * nh * sizeof(uint64_t)), "pengk_memset");
   const int both = both_strands ? 1 : 0;
-  check(pengk_motif_scan(ctx, d_words.get(), d_valid.get(), d_offs.get(), d_lens.get(), n_local, n_motifs, S.data(),
+  check(pengk_motif_scan(ctx, in.d_words.get(), in.d_valid.get(), in.d_offs.get(), in.d_lens.get(), n_local, n_motifs, S.data(),
                          len.data(), both, d_best.get()),
         "pengk_motif_scan");
   check(pengk_score_histograms(ctx, n_motifs, d_best.get(), n_local, lo.data(), hi.data(), hoffs.data(), d_hist.get()),
         "pengk_score_histograms");
-  check(pengk_sample_background(ctx, seed, set.getLocalBase(), n_local, d_offs.get(), d_lens.get(), K, thr.data(), d_neg.get()),
+  check(pengk_sample_background(ctx, seed, set.getLocalBase(), n_local, in.d_offs.get(), in.d_lens.get(), K, thr.data(), d_neg.get()),
         "pengk_sample_background");
-  check(pengk_motif_scan(ctx, d_neg.get(), nullptr, d_offs.get(), d_lens.get(), n_local, n_motifs, S.data(), len.data(), both,
+  check(pengk_motif_scan(ctx, d_neg.get(), nullptr, in.d_offs.get(), in.d_lens.get(), n_local, n_motifs, S.data(), len.data(), both,
                          d_best.get()),
         "pengk_motif_scan");
   check(pengk_score_histograms(ctx, n_motifs, d_best.get(), n_local, lo.data(), hi.data(), hoffs.data(), d_hist.get() + nh),

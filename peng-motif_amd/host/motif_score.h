@@ -12,6 +12,25 @@
 #include "shared/BackgroundModel.h"
 #include "shared/SequenceSet.h"
 
+#include "device.h"
+
+// The scan layout (include/pengk.h) of this rank's records of a set, on the device: built once for the scoring and the
+// sites (--score-motifs, --sites).  The set must still hold its byte codes (pengk_host::keep_host_codes).
+struct ScanInput {
+  size_t n_local = 0;
+  uint64_t n_words = 0;
+  pengk_host::DeviceBuffer<uint64_t> d_words;
+  pengk_host::DeviceBuffer<uint32_t> d_valid;
+  pengk_host::DeviceBuffer<int64_t> d_offs;
+  pengk_host::DeviceBuffer<uint32_t> d_lens;
+};
+void build_scan_input(SequenceSet& set, ScanInput* in);
+
+// S[(m * PENGK_MAX_MOTIF_LEN + j) * 4 + a] = clamp(lround(100 log2(pwm / bg0)), -2000, 2000) and len[m] of every motif
+// (a motif wider than PENGK_MAX_MOTIF_LEN ends the program; `who` names the step in the message)
+void motif_log_odds(const std::vector<IUPACPattern*>& pats, const float* bg0, std::vector<int32_t>& S, std::vector<int32_t>& len,
+                    const char* who);
+
 struct MotifScore {
   double zoops_score = 0.0;  // AUC of the best window scores, input against sampled sequences
   double occur = 0.0;        // share of input sequences with a site, estimated at 1 % false positives
@@ -20,7 +39,7 @@ struct MotifScore {
 // Scores pats (in their order) over this rank's records of `set` and the negatives of their global indices; the
 // histograms are summed over the ranks, so every rank gets the scores of the whole input.  K: the order of the
 // sampling model (--bg-model-order), V from bg.  Collective in a multi-rank run.
-std::vector<MotifScore> score_motifs(const std::vector<IUPACPattern*>& pats, SequenceSet& set, BackgroundModel& bg, int K,
-                                     bool both_strands, uint64_t seed);
+std::vector<MotifScore> score_motifs(const std::vector<IUPACPattern*>& pats, SequenceSet& set, const ScanInput& in,
+                                     BackgroundModel& bg, int K, bool both_strands, uint64_t seed);
 
 #endif

@@ -124,11 +124,12 @@ class SequenceSet {
   // codes()[offsets()[i] .. offsets()[i+1])
   const uint8_t* codes() { return flatten(), flat_codes_; }
   const int64_t* offsets() { return flatten(), flat_offs_.data(); }
+  // the FASTA header of local record k without '>' (an empty one: the record's 1-based global index)
+  std::string header(size_t k) const;
 
  private:
   void readFASTA(const SequenceChunkSink& sink);
   void flatten();
-  std::string header(size_t k) const;  // of local record k
   std::string path_;
   std::string diagnostics_;
   bool single_stranded_;
