@@ -409,6 +409,49 @@ int pengk_sites_emit(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_
                      int both_strands, const int32_t* h_thr, const uint64_t* d_counts, uint64_t i0, uint64_t i1,
                      pengk_site* d_sites, uint64_t cap);
 
+/* ---- central enrichment (--centrality: which found motifs sit at the centres of the input sequences; CentriMo's
+ *      site distribution and binomial test) ------------------------------------------------------------
+ * Over the scan layout and the integer log-odds of pengk_motif_scan.  One best window strand per (motif, sequence); the
+ * offsets of those at or above the motif's threshold binned on the device; the test on the host.  Integer up to the
+ * summary: any slicing, any rank count and a numpy restatement give the same histograms. */
+#define PENGK_CENTRALITY_MAX_LEN 65536 /* longer sequences are not considered */
+/* Replaces CentriMo's per-sequence best-site search.  The best window strand of every motif on every sequence:
+ * d_best[m * n_seq + i] its score (PENGK_SCORE_SENTINEL without a window of A/C/G/T only), d_site[m * n_seq + i] = 2p + s
+ * (p its 0-based start in + coordinates, s 0 for +, 1 for -; 0 without a window).  Best = the largest (score, key), key =
+ * mix64(mix64(0x9E3779B97F4A7C15 * (g + 1) ^ m) ^ (2p + s)) mod 2^64 (mix64 = the splitmix64 finalizer, g = seq0 + i the
+ * sequence's global index, m the motif index); an equal key: the smaller p, then +.  A deterministic, uniform tie-break
+ * that no shard boundary changes.  Other arguments as pengk_motif_scan (both_strands 0: + only). */
+int pengk_motif_best_sites(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_valid, const int64_t* d_offs,
+                           const uint32_t* d_lens, uint64_t n_seq, uint64_t seq0, int n_motifs, const int32_t* h_S,
+                           const int32_t* h_len, int both_strands, int32_t* d_best, uint64_t* d_site);
+/* Replaces CentriMo's site-position counts.  For every motif m and every sequence i with h_len[m] <= L <= max_len (L =
+ * d_lens[i]; 1 <= max_len <= PENGK_CENTRALITY_MAX_LEN) whose best score (d_best, d_site from pengk_motif_best_sites) is
+ * >= h_thr[m]: ADDS 1 to d_hist_offsets[m * (2 max_len + 1) + max_len + d], d = 2p + w - L (twice the distance of the
+ * site's centre from the sequence's centre), and to d_hist_lengths[m * (max_len + 1) + L].  uint64, caller-zeroed. */
+int pengk_centrality_histograms(pengk_ctx* ctx, int n_motifs, const int32_t* d_best, const uint64_t* d_site,
+                                const uint32_t* d_lens, uint64_t n_seq, const int32_t* h_len, const int32_t* h_thr,
+                                uint32_t max_len, uint64_t* d_hist_offsets, uint64_t* d_hist_lengths);
+typedef struct {
+  uint64_t sites;        /* N: sequences with a site */
+  uint32_t max_offset;   /* Dm: the largest L - w among them */
+  uint32_t window;       /* r: the window |d| <= r with the smallest p-value (center_distance = r / 2) */
+  uint64_t in_window;    /* K(r) */
+  double expected;       /* N * mean of f(L, w, r) over the sites' sequences */
+  double log10_pvalue;   /* log10 P(X >= K), X ~ Binomial(N, expected / N) */
+  double log10_evalue;   /* log10_pvalue + log10(Dm + 1) + log10(n_motifs) */
+} pengk_centrality;
+/* Pure CPU.  Replaces CentriMo's binomial test.  From one motif's two histograms (max_len as above, w its width,
+ * n_motifs the motifs of the run, for the Bonferroni factor): with N = 0 only `sites` is set (0) and the rest is 0.
+ * Otherwise, for each r in 0..Dm, K(r) = #{|d| <= r}, p(r) = (1/N) sum_L n_L f(L, w, r), f(L, w, r) = #{p in 0..L-w :
+ * |2p + w - L| <= r} / (L - w + 1), and P(r) = P(X >= K(r)) for X ~ Binomial(N, p(r)) -- exact for equal lengths,
+ * conservative for mixed ones (Hoeffding 1956).  `window` is the r with the smallest log10 P(r), the smaller r on ties;
+ * an r at which no sequence can have an offset is a tie with r - 1 (or has p = 0 at r = 0) and is never reported.  Cost:
+ * O(Dm + max_len) to build every p(r); the tail by a continued fraction in log space (no underflow). */
+int pengk_centrality_summary(const uint64_t* h_hist_offsets, const uint64_t* h_hist_lengths, uint32_t max_len, int w,
+                             int n_motifs, pengk_centrality* out);
+/* Pure CPU.  log10 P(X >= k), X ~ Binomial(n, p), k <= n, 0 <= p <= 1: the tail pengk_centrality_summary uses. */
+int pengk_binomial_log10_sf(uint64_t n, uint64_t k, double p, double* out);
+
 /* Self-test of the division sequence the serial EM's weights kernel uses where a PWM's operand ranges allow (the IEEE
  * division's instructions without its range scaling: csrc/em.hip, lean_div; src/peng.cpp:124-125, 186 are the three
  * divisions of a weight).  4096 x 256 threads draw pairs_per_thread random operand pairs each, keep those inside the

@@ -34,11 +34,18 @@ EXPORTS = [
     "pengk_scan_layout_words", "pengk_scan_layout_build", "pengk_synth_scan_sequences", "pengk_sample_background",
     "pengk_motif_scan", "pengk_score_histograms", "pengk_score_summary",
     "pengk_score_tail_pvalues", "pengk_score_threshold", "pengk_sites_count", "pengk_sites_slices", "pengk_sites_emit",
+    "pengk_motif_best_sites", "pengk_centrality_histograms", "pengk_centrality_summary", "pengk_binomial_log10_sf",
 ]
 MAX_MOTIF_LEN = 64
 SCORE_SENTINEL = -2 ** 31
 SITES_BLOCK = 4096
 SITE = np.dtype([("seq", np.uint32), ("pos", np.uint32), ("score", np.int32), ("motif_strand", np.uint32)])
+CENTRALITY_MAX_LEN = 65536
+
+
+class CentralityStruct(C.Structure):
+    _fields_ = [("sites", C.c_uint64), ("max_offset", C.c_uint32), ("window", C.c_uint32), ("in_window", C.c_uint64),
+                ("expected", C.c_double), ("log10_pvalue", C.c_double), ("log10_evalue", C.c_double)]
 
 
 class PengkError(RuntimeError):
@@ -137,6 +144,10 @@ def lib():
         L.pengk_sites_count.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, vp, vp, C.c_int, vp, vp]
         L.pengk_sites_slices.argtypes = [vp, vp, u64, C.c_int, vp, u64, vp, vp, C.POINTER(u64)]
         L.pengk_sites_emit.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, vp, vp, C.c_int, vp, vp, u64, u64, vp, u64]
+        L.pengk_motif_best_sites.argtypes = [vp, vp, vp, vp, vp, u64, u64, C.c_int, vp, vp, C.c_int, vp, vp]
+        L.pengk_centrality_histograms.argtypes = [vp, C.c_int, vp, vp, vp, u64, vp, vp, C.c_uint32, vp, vp]
+        L.pengk_centrality_summary.argtypes = [vp, vp, C.c_uint32, C.c_int, C.c_int, C.POINTER(CentralityStruct)]
+        L.pengk_binomial_log10_sf.argtypes = [u64, u64, C.c_double, C.POINTER(C.c_double)]
         _lib = L
     return _lib
 
@@ -215,6 +226,24 @@ def score_threshold(tail, lo, p):
     t = C.c_int32()
     _check(lib().pengk_score_threshold(tail.ctypes.data, lo, lo + len(tail) - 1, p, C.byref(t)))
     return t.value
+
+
+def centrality_summary(hist_offsets, hist_lengths, max_len, w, n_motifs):
+    """one motif's central-enrichment test from its two histograms (pengk_centrality_summary, CPU): a dict with sites,
+    max_offset, window, in_window, expected, log10_pvalue, log10_evalue"""
+    hd = np.ascontiguousarray(hist_offsets, np.uint64)
+    hl = np.ascontiguousarray(hist_lengths, np.uint64)
+    assert len(hd) == 2 * max_len + 1 and len(hl) == max_len + 1
+    out = CentralityStruct()
+    _check(lib().pengk_centrality_summary(hd.ctypes.data, hl.ctypes.data, max_len, w, n_motifs, C.byref(out)))
+    return {k: getattr(out, k) for k, _ in CentralityStruct._fields_}
+
+
+def binomial_log10_sf(n, k, p):
+    """log10 P(X >= k) for X ~ Binomial(n, p) (pengk_binomial_log10_sf, CPU)"""
+    out = C.c_double()
+    _check(lib().pengk_binomial_log10_sf(int(n), int(k), float(p), C.byref(out)))
+    return out.value
 
 
 def _pad_motifs(S, lens):
@@ -538,6 +567,34 @@ class Context:
                 out["score"][j:j + k] = sel["score"]
                 j += k
         return out, tot
+
+    # ---- central enrichment (--centrality) ------------------------------------------------------------------
+    def motif_best_sites(self, scan, S, lens, both, seq0=0, best=None, site=None):
+        """(best, site): the best score and 2p + s of every motif on every sequence of `scan` (device int32 / uint64,
+        n_motifs x n_seq); seq0 = the global index of the scan's first sequence (it seeds the tie-break)"""
+        n = len(lens)
+        Sp, ln = _pad_motifs(S, lens)
+        if best is None:
+            best = self.empty((max(n, 1), max(scan[4], 1)), np.int32)
+        if site is None:
+            site = self.empty((max(n, 1), max(scan[4], 1)), np.uint64)
+        _check(lib().pengk_motif_best_sites(self.h, _ptr(scan[0]), _ptr(scan[1]), _ptr(scan[2]), _ptr(scan[3]), scan[4], seq0, n,
+                                            Sp.ctypes.data, ln.ctypes.data, int(both), _ptr(best), _ptr(site)))
+        return best, site
+
+    def centrality_histograms(self, best, site, lens_dev, n_seq, widths, thr, max_len, hd=None, hl=None):
+        """(hd, hl) device uint64, n_motifs x (2 max_len + 1) offset bins and n_motifs x (max_len + 1) length bins, ADDED
+        to (allocated zeroed if None)"""
+        n = len(widths)
+        w = np.ascontiguousarray(widths, np.int32)
+        th = np.ascontiguousarray(thr, np.int32)
+        if hd is None:
+            hd = self.to_device(np.zeros((max(n, 1), 2 * max_len + 1), np.uint64))
+        if hl is None:
+            hl = self.to_device(np.zeros((max(n, 1), max_len + 1), np.uint64))
+        _check(lib().pengk_centrality_histograms(self.h, n, _ptr(best), _ptr(site), _ptr(lens_dev), n_seq, w.ctypes.data,
+                                                 th.ctypes.data, max_len, _ptr(hd), _ptr(hl)))
+        return hd, hl
 
     def em_device(self, W, n_pwm, d_pwms, counts, bg, d_state, d_change, saturation=1e4, threshold=0.08, max_iterations=10):
         _check(lib().pengk_em_device(self.h, W, n_pwm, _ptr(d_pwms), saturation, threshold, max_iterations, _ptr(counts),

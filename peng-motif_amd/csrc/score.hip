@@ -12,6 +12,8 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
+#include <cstdlib>
 #include <vector>
 
 #include "pengk_internal.h"
@@ -463,6 +465,127 @@ __global__ __launch_bounds__(SITES_THREADS) void xscan_apply_kernel(const unsign
   }
 }
 
+// ---- central enrichment (pengk_motif_best_sites, pengk_centrality_histograms) --------------------------
+constexpr uint64_t GOLDEN = 0x9E3779B97F4A7C15ull;
+constexpr int CENT_LDS_BINS = 16384;  // offset and length bins of one motif in LDS (64 KiB) when they all fit, else global
+
+// the best window strand of every motif on every sequence: the largest (score, key), key = mix64(h ^ (2p + s)),
+// h = mix64(GOLDEN * (g + 1) ^ m); an equal key keeps the earlier window strand, which the scan order (p, then + before
+// -) makes the smaller (p, s).  Keys are computed on ties only: the best's own key once, then the challenger's.
+template <bool BOTH>
+struct BestSiteVisit {
+  const MotifRec* mrec;
+  int32_t* best_out;
+  unsigned long long* site_out;
+  uint64_t n_seq, i, g;
+  int32_t b[SCAN_PASS];
+  uint64_t c[SCAN_PASS];   // 2p + s of the best
+  uint64_t h[SCAN_PASS];
+  uint64_t kb[SCAN_PASS];  // its key, once kv
+  bool kv[SCAN_PASS];
+  __device__ __forceinline__ void begin(int q, int r) {
+    b[q] = PENGK_SCORE_SENTINEL;
+    c[q] = 0;
+    kv[q] = false;
+    h[q] = mix64((GOLDEN * (g + 1)) ^ (uint64_t)mrec[r].m);
+  }
+  __device__ __forceinline__ void offer(int q, uint64_t cand, int32_t sc) {
+    if (sc > b[q]) {
+      b[q] = sc;
+      c[q] = cand;
+      kv[q] = false;
+      return;
+    }
+    if (!kv[q]) {
+      kb[q] = mix64(h[q] ^ c[q]);
+      kv[q] = true;
+    }
+    const uint64_t k = mix64(h[q] ^ cand);
+    if (k > kb[q]) {
+      c[q] = cand;
+      kb[q] = k;
+    }
+  }
+  __device__ __forceinline__ void window(int q, uint32_t pos, int32_t sf, int32_t sr) {
+    if (sf >= b[q]) offer(q, 2ull * pos, sf);
+    if (BOTH && sr >= b[q]) offer(q, 2ull * pos + 1ull, sr);
+  }
+  __device__ __forceinline__ void end(int q, int r) {
+    const uint64_t o = (uint64_t)mrec[r].m * n_seq + i;
+    best_out[o] = b[q];
+    site_out[o] = c[q];
+  }
+};
+
+// a kernel of its own: the visitor's state (key, site) stays out of the scoring and sites kernels
+template <bool BOTH>
+__global__ __launch_bounds__(SCAN_THREADS) void motif_best_site_kernel(const uint64_t* __restrict__ words,
+                                                                       const uint32_t* __restrict__ valid,
+                                                                       const int64_t* __restrict__ offs,
+                                                                       const uint32_t* __restrict__ lens, uint64_t n_seq,
+                                                                       uint64_t seq0, const int32_t* __restrict__ tables,
+                                                                       const MotifRec* __restrict__ recs,
+                                                                       const GroupRec* __restrict__ groups,
+                                                                       int32_t* __restrict__ best_out,
+                                                                       unsigned long long* __restrict__ site_out) {
+  __shared__ int32_t tab[SCAN_TABLES * 256];
+  __shared__ MotifRec mrec[SCAN_MAX_MOTIFS];
+  const GroupRec g = groups[blockIdx.y];
+  for (int t = threadIdx.x; t < g.n_ints; t += SCAN_THREADS) tab[t] = tables[g.table0 + t];
+  for (int t = threadIdx.x; t < g.m1 - g.m0; t += SCAN_THREADS) mrec[t] = recs[g.m0 + t];
+  __syncthreads();
+  for (uint64_t i = blockIdx.x * (uint64_t)SCAN_THREADS + threadIdx.x; i < n_seq; i += (uint64_t)gridDim.x * SCAN_THREADS) {
+    const uint32_t L = lens[i];
+    const uint64_t w0 = (uint64_t)offs[i] >> 5;
+    BestSiteVisit<BOTH> v{mrec, best_out, site_out, n_seq, i, seq0 + i, {}, {}, {}, {}, {}};
+    walk_sequence<BOTH>(words + w0, valid ? valid + w0 : nullptr, L, tab, mrec, g.m1 - g.m0, v);
+  }
+}
+
+// per motif (blockIdx.y): the best sites at or above its threshold of the sequences with w <= L <= max_len, ADDED to
+// the offset bins hd[m * (2 max_len + 1) + max_len + d], d = 2p + w - L, and the length bins hl[m * (max_len + 1) + L].
+// LDS: every bin of the motif in LDS (equal lengths send all counts to a few bins), flushed once per block.
+template <bool LDS>
+__global__ __launch_bounds__(HIST_THREADS) void centrality_hist_kernel(const int32_t* __restrict__ best,
+                                                                       const unsigned long long* __restrict__ site,
+                                                                       const uint32_t* __restrict__ lens, uint64_t n_seq,
+                                                                       const int32_t* __restrict__ wt, uint32_t max_len,
+                                                                       unsigned long long* __restrict__ hd,
+                                                                       unsigned long long* __restrict__ hl) {
+  __shared__ uint32_t h[LDS ? CENT_LDS_BINS : 1];
+  const int m = blockIdx.y;
+  const uint32_t w = (uint32_t)wt[2 * m];
+  const int32_t t = wt[2 * m + 1];
+  const uint32_t nd = 2 * max_len + 1, nl = max_len + 1;
+  unsigned long long* HD = hd + (uint64_t)m * nd;
+  unsigned long long* HL = hl + (uint64_t)m * nl;
+  if (LDS) {
+    for (uint32_t k = threadIdx.x; k < nd + nl; k += HIST_THREADS) h[k] = 0;
+    __syncthreads();
+  }
+  const int32_t* B = best + (uint64_t)m * n_seq;
+  const unsigned long long* C = site + (uint64_t)m * n_seq;
+  for (uint64_t i = blockIdx.x * (uint64_t)HIST_THREADS + threadIdx.x; i < n_seq; i += (uint64_t)gridDim.x * HIST_THREADS) {
+    const uint32_t L = lens[i];
+    if (B[i] < t || L > max_len || L < w) continue;
+    const uint64_t p = C[i] >> 1;
+    if (p > L - w) continue;  // (not a window of this sequence: no bin)
+    const uint32_t bd = 2 * (uint32_t)p + w + max_len - L;  // max_len + d, in [max_len - (L - w), max_len + (L - w)]
+    if (LDS) {
+      atomicAdd(&h[bd], 1u);
+      atomicAdd(&h[nd + L], 1u);
+    } else {
+      atomicAdd(&HD[bd], 1ull);
+      atomicAdd(&HL[L], 1ull);
+    }
+  }
+  if (LDS) {
+    __syncthreads();
+    for (uint32_t k = threadIdx.x; k < nd + nl; k += HIST_THREADS)
+      if (h[k]) atomicAdd(k < nd ? &HD[k] : &HL[k - nd], (unsigned long long)h[k]);
+  }
+}
+
 int grid_for(pengk_ctx* ctx, uint64_t work, uint32_t per_block, uint32_t per_cu) {
   const uint64_t need = (work + per_block - 1) / per_block;
   const uint64_t cap = (uint64_t)ctx->num_cu * per_cu;
@@ -551,6 +674,47 @@ int stage_motifs(pengk_ctx* ctx, int n_motifs, const int32_t* h_S, const int32_t
   out->thr = hb ? (const int32_t*)(base + tb + rb + gb) : nullptr;
   out->n_groups = (int)groups.size();
   return PENGK_OK;
+}
+
+// Lentz's continued fraction of the regularised incomplete beta: I_x(a, b) = x^a (1-x)^b / (a B(a, b)) * betacf(a, b, x),
+// fast to converge for x < (a + 1) / (a + b + 2) (Numerical Recipes 6.4)
+double betacf(double a, double b, double x) {
+  const double FPMIN = 1e-300, EPS = 1e-16;
+  const double qab = a + b, qap = a + 1.0, qam = a - 1.0;
+  auto tiny = [&](double v) { return std::fabs(v) < FPMIN ? FPMIN : v; };
+  double c = 1.0, d = 1.0 / tiny(1.0 - qab * x / qap), h = d;
+  for (int64_t i = 1; i <= (1 << 22); ++i) {
+    const double m = (double)i, m2 = 2.0 * m;
+    double aa = m * (b - m) * x / ((qam + m2) * (a + m2));
+    d = 1.0 / tiny(1.0 + aa * d);
+    c = tiny(1.0 + aa / c);
+    h *= d * c;
+    aa = -(a + m) * (qab + m) * x / ((a + m2) * (qap + m2));
+    d = 1.0 / tiny(1.0 + aa * d);
+    c = tiny(1.0 + aa / c);
+    const double del = d * c;
+    h *= del;
+    if (std::fabs(del - 1.0) < EPS) break;
+  }
+  return h;
+}
+
+// log10 P(X >= k) for X ~ Binomial(n, p) = log10 I_p(k, n - k + 1), in log space throughout: no underflow however small
+// the tail (CentriMo's binomial test, which reports the same tail)
+double log10_binomial_sf(uint64_t n, uint64_t k, double p) {
+  if (k == 0 || p >= 1.0) return 0.0;
+  if (p <= 0.0) return -INFINITY;
+  const double a = (double)k, b = (double)(n - k) + 1.0;
+  const double lbeta = std::lgamma(a) + std::lgamma(b) - std::lgamma(a + b);
+  const double lfront = a * std::log(p) + b * std::log1p(-p) - lbeta;
+  double ln;
+  if (p < (a + 1.0) / (a + b + 2.0)) {
+    ln = lfront - std::log(a) + std::log(betacf(a, b, p));
+  } else {  // the upper tail is the larger part: 1 - I_{1-p}(b, a)
+    const double q = std::exp(lfront - std::log(b)) * betacf(b, a, 1.0 - p);
+    ln = q < 1.0 ? std::log1p(-q) : lfront - std::log(a) + std::log(betacf(a, b, p));  // (rounding: the direct form)
+  }
+  return ln / std::log(10.0);
 }
 
 }  // namespace
@@ -919,6 +1083,141 @@ int pengk_sites_emit(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_
     hipLaunchKernelGGL((motif_sites_kernel<false, true>), grid, dim3(SCAN_THREADS), 0, ctx->stream, d_words, d_valid, d_offs, d_lens, i0,
                        i1, n_seq, st.tables, st.recs, st.groups, st.thr, nullptr, so, d_sites, cap);
   PENGK_HIP(hipGetLastError());
+  return PENGK_OK;
+}
+
+int pengk_motif_best_sites(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_valid, const int64_t* d_offs,
+                           const uint32_t* d_lens, uint64_t n_seq, uint64_t seq0, int n_motifs, const int32_t* h_S,
+                           const int32_t* h_len, int both_strands, int32_t* d_best, uint64_t* d_site) {
+  if (!ctx || n_motifs < 0 || (n_motifs && (!h_S || !h_len)) ||
+      (n_seq && n_motifs && (!d_words || !d_offs || !d_lens || !d_best || !d_site)))
+    return fail(PENGK_ERR_ARG, "pengk_motif_best_sites: bad argument");
+  int rc = check_motifs("pengk_motif_best_sites", n_motifs, h_S, h_len);
+  if (rc) return rc;
+  SCORE_ENTER(ctx);
+  if (n_seq == 0 || n_motifs == 0) return PENGK_OK;
+  StagedMotifs st;
+  rc = stage_motifs(ctx, n_motifs, h_S, h_len, both_strands ? 2 : 1, nullptr, &st);
+  if (rc) return rc;
+  const dim3 grid(grid_for(ctx, n_seq, SCAN_THREADS, 8), (unsigned)st.n_groups);
+  unsigned long long* site = (unsigned long long*)d_site;
+  if (both_strands)
+    hipLaunchKernelGGL(motif_best_site_kernel<true>, grid, dim3(SCAN_THREADS), 0, ctx->stream, d_words, d_valid, d_offs, d_lens,
+                       n_seq, seq0, st.tables, st.recs, st.groups, d_best, site);
+  else
+    hipLaunchKernelGGL(motif_best_site_kernel<false>, grid, dim3(SCAN_THREADS), 0, ctx->stream, d_words, d_valid, d_offs, d_lens,
+                       n_seq, seq0, st.tables, st.recs, st.groups, d_best, site);
+  PENGK_HIP(hipGetLastError());
+  return PENGK_OK;
+}
+
+int pengk_centrality_histograms(pengk_ctx* ctx, int n_motifs, const int32_t* d_best, const uint64_t* d_site,
+                                const uint32_t* d_lens, uint64_t n_seq, const int32_t* h_len, const int32_t* h_thr,
+                                uint32_t max_len, uint64_t* d_hist_offsets, uint64_t* d_hist_lengths) {
+  if (!ctx || n_motifs < 0 || max_len < 1 || max_len > PENGK_CENTRALITY_MAX_LEN ||
+      (n_motifs && (!h_len || !h_thr || !d_hist_offsets || !d_hist_lengths)) || (n_seq && n_motifs && (!d_best || !d_site || !d_lens)))
+    return fail(PENGK_ERR_ARG, "pengk_centrality_histograms: bad argument");
+  for (int m = 0; m < n_motifs; ++m)
+    if (h_len[m] < 1 || h_len[m] > PENGK_MAX_MOTIF_LEN)
+      return fail(PENGK_ERR_ARG, "pengk_centrality_histograms: motif %d has width %d (1..%d)", m, h_len[m], PENGK_MAX_MOTIF_LEN);
+  SCORE_ENTER(ctx);
+  if (n_seq == 0 || n_motifs == 0) return PENGK_OK;
+  std::vector<int32_t> wt(2 * (size_t)n_motifs);
+  for (int m = 0; m < n_motifs; ++m) {
+    wt[2 * m] = h_len[m];
+    wt[2 * m + 1] = h_thr[m];
+  }
+  int rc = ensure_scratch(ctx, &ctx->d_misc, &ctx->misc_bytes, wt.size() * sizeof(int32_t));
+  if (rc) return rc;
+  PENGK_HIP(hipStreamSynchronize(ctx->stream));
+  PENGK_HIP(hipMemcpy(ctx->d_misc, wt.data(), wt.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  const uint64_t per_motif = std::max<uint64_t>(1, std::min<uint64_t>((n_seq + HIST_THREADS - 1) / HIST_THREADS,
+                                                                      (uint64_t)ctx->num_cu * 2 / (uint64_t)n_motifs + 1));
+  const dim3 grid((unsigned)per_motif, (unsigned)n_motifs);
+  const bool lds = 3ull * max_len + 2 <= (uint64_t)CENT_LDS_BINS && n_seq >= (uint64_t)HIST_THREADS * 16;
+  const unsigned long long* site = (const unsigned long long*)d_site;
+  unsigned long long* hd = (unsigned long long*)d_hist_offsets;
+  unsigned long long* hl = (unsigned long long*)d_hist_lengths;
+  if (lds)
+    hipLaunchKernelGGL(centrality_hist_kernel<true>, grid, dim3(HIST_THREADS), 0, ctx->stream, d_best, site, d_lens, n_seq,
+                       (const int32_t*)ctx->d_misc, max_len, hd, hl);
+  else
+    hipLaunchKernelGGL(centrality_hist_kernel<false>, grid, dim3(HIST_THREADS), 0, ctx->stream, d_best, site, d_lens, n_seq,
+                       (const int32_t*)ctx->d_misc, max_len, hd, hl);
+  PENGK_HIP(hipGetLastError());
+  return PENGK_OK;
+}
+
+int pengk_binomial_log10_sf(uint64_t n, uint64_t k, double p, double* out) {
+  if (!out || k > n || !(p >= 0.0 && p <= 1.0)) return fail(PENGK_ERR_ARG, "pengk_binomial_log10_sf: bad argument");
+  *out = log10_binomial_sf(n, k, p);
+  return PENGK_OK;
+}
+
+int pengk_centrality_summary(const uint64_t* h_hist_offsets, const uint64_t* h_hist_lengths, uint32_t max_len, int w,
+                             int n_motifs, pengk_centrality* out) {
+  if (!h_hist_offsets || !h_hist_lengths || !out || max_len < 1 || max_len > PENGK_CENTRALITY_MAX_LEN || w < 1 ||
+      w > PENGK_MAX_MOTIF_LEN || n_motifs < 1)
+    return fail(PENGK_ERR_ARG, "pengk_centrality_summary: bad argument");
+  memset(out, 0, sizeof *out);
+  const int64_t C0 = max_len;  // bin of d = 0
+  // N, Dm and the sites' offsets against the lengths they can come from
+  uint64_t N = 0, Nd = 0;
+  int64_t Dm = -1;
+  for (uint32_t L = 0; L <= max_len; ++L) {
+    const uint64_t n = h_hist_lengths[L];
+    if (!n) continue;
+    if ((int64_t)L < w) return fail(PENGK_ERR_ARG, "pengk_centrality_summary: sites on a sequence shorter than the motif");
+    N += n;
+    Dm = (int64_t)L - w;
+  }
+  for (int64_t b = 0; b <= 2 * C0; ++b) {
+    const uint64_t n = h_hist_offsets[b];
+    if (!n) continue;
+    if (std::abs(b - C0) > Dm) return fail(PENGK_ERR_ARG, "pengk_centrality_summary: offset beyond the longest sequence");
+    Nd += n;
+  }
+  if (N != Nd) return fail(PENGK_ERR_ARG, "pengk_centrality_summary: the histograms hold different totals");
+  out->sites = N;
+  if (N == 0) return PENGK_OK;
+  out->max_offset = (uint32_t)Dm;
+  // N p(r) = sum_L n_L #{p : |2p + w - L| <= r} / (D + 1), D = L - w: #{...} = D + 1 for r >= D, else r + [r = D mod 2].
+  // By D: N p(r) = r (A_0(r) + A_1(r)) + A_{r mod 2}(r) + B(r) with A_par(r) = sum over D > r, D = par (mod 2) of
+  // n_D / (D + 1) and B(r) = sum over D <= r of n_D -- suffix and prefix sums: O(Dm + lengths), not their product.
+  const size_t nD = (size_t)Dm + 1;
+  std::vector<double> A0(nD + 1, 0.0), A1(nD + 1, 0.0);  // A_par over D >= r (shifted by one below)
+  std::vector<uint64_t> cnt(nD, 0), hit0(nD + 1, 0), hit1(nD + 1, 0);  // n_D; sites of D >= r by parity
+  for (int64_t D = 0; D <= Dm; ++D) cnt[D] = h_hist_lengths[D + w];
+  for (int64_t D = Dm; D >= 0; --D) {
+    const double c = (double)cnt[D] / (double)(D + 1);
+    A0[D] = A0[D + 1] + ((D & 1) ? 0.0 : c);
+    A1[D] = A1[D + 1] + ((D & 1) ? c : 0.0);
+    hit0[D] = hit0[D + 1] + ((D & 1) ? 0 : cnt[D]);
+    hit1[D] = hit1[D + 1] + ((D & 1) ? cnt[D] : 0);
+  }
+  uint64_t below = 0, K = h_hist_offsets[C0];
+  double best = 0.0;
+  bool have = false;
+  for (int64_t r = 0; r <= Dm; ++r) {
+    below += cnt[r];  // B(r)
+    if (r) K += h_hist_offsets[C0 - r] + h_hist_offsets[C0 + r];
+    // r is a window of its own only if a sequence has an offset of its parity at distance r: otherwise p(r) and K(r)
+    // equal those of r - 1 exactly (and p(0) = K(0) = 0), a tie that the smaller r wins
+    if (((r & 1) ? hit1[r] : hit0[r]) == 0) continue;
+    const double a0 = A0[r + 1], a1 = A1[r + 1];
+    const double np = (double)r * (a0 + a1) + ((r & 1) ? a1 : a0) + (double)below;
+    const double pbar = std::min(1.0, np / (double)N);
+    const double lp = log10_binomial_sf(N, K, pbar);
+    if (!have || lp < best) {
+      have = true;
+      best = lp;
+      out->window = (uint32_t)r;
+      out->in_window = K;
+      out->expected = np;
+      out->log10_pvalue = lp;
+    }
+  }
+  out->log10_evalue = out->log10_pvalue + std::log10((double)(Dm + 1)) + std::log10((double)n_motifs);
   return PENGK_OK;
 }
 

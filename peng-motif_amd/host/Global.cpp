@@ -46,13 +46,16 @@ bool Global::scoreMotifs = false;
 unsigned long long Global::scoreSeed = 1;
 char* Global::sitesFilename = nullptr;
 double Global::sitesPvalue = 1e-4;
+char* Global::centralityFilename = nullptr;
+double Global::centralityPvalue = 1e-4;
 
 void Global::init(int nargs, char* args[]) {
   readArguments(nargs, args);
   Alphabet::init(alphabetType);
   pengk_host::start_context();  // the device runtime starts while the FASTA files are read
   pengk_host::start_sharded_ingest();  // multi-GPU run: every rank reads its own byte range of the files
-  pengk_host::keep_host_codes(scoreMotifs || sitesFilename);  // (the scoring and the sites scan the input after the motifs are found)
+  // (the scoring, the sites and the centrality scan the input after the motifs are found)
+  pengk_host::keep_host_codes(scoreMotifs || sitesFilename || centralityFilename);
   // both strands are handled inside the count; sequences are always read single stranded
   // ... and every chunk of the input set is packed and sent to the device while the rest is still being read
   pengk_host::begin_streaming_pack(patternLength);
@@ -205,6 +208,17 @@ void Global::readArguments(int nargs, char* args[]) {
         log_line("ERROR", "--sites-pvalue must be a number in (0, 1]");
         exit(4);
       }
+    } else if (!strcmp(a, "--centrality")) {
+      centralityFilename = (char*)need(i, nargs, args, printHelp);
+    } else if (!strcmp(a, "--centrality-pvalue")) {
+      const char* v = need(i, nargs, args, printHelp);
+      char* end = nullptr;
+      centralityPvalue = std::strtod(v, &end);
+      if (end == v || *end || !(centralityPvalue > 0.0 && centralityPvalue <= 1.0)) {
+        printHelp();
+        log_line("ERROR", "--centrality-pvalue must be a number in (0, 1]");
+        exit(4);
+      }
     } else if (!strcmp(a, "--version")) {
       std::cout << "peng_motif " << VERSION_NUMBER << std::endl;  // (src/Global.cpp:299-301: without the word)
       exit(0);
@@ -250,6 +264,9 @@ void Global::printHelp() {
   printf("  --sites FILE                   write every occurrence of the motifs (TSV: sequence, position, strand,\n");
   printf("                                 score, p-value) at p-value --sites-pvalue or below\n");
   printf("  --sites-pvalue FLOAT           p-value threshold of --sites, in (0, 1] (default 1e-4)\n");
+  printf("  --centrality FILE              test every motif for enrichment at the sequence centres (TSV: best site\n");
+  printf("                                 per sequence at p-value --centrality-pvalue or below, binomial test)\n");
+  printf("  --centrality-pvalue FLOAT      p-value threshold of a best site, in (0, 1] (default 1e-4)\n");
   printf("  --threads INT                  accepted for compatibility\n");
   printf("  --device INT                   HIP device index (default 0)\n");
   printf("  -v INT                         verbosity\n");

@@ -61,6 +61,8 @@ class Global {
   static unsigned long long scoreSeed;       // --score-seed
   static char* sitesFilename;                // --sites (new: every motif occurrence with its p-value)
   static double sitesPvalue;                 // --sites-pvalue
+  static char* centralityFilename;           // --centrality (new: central enrichment of the motifs)
+  static double centralityPvalue;            // --centrality-pvalue
 
   static void init(int nargs, char* args[]);
   static void destruct();

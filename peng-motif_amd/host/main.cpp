@@ -14,6 +14,7 @@
 #include "device.h"
 #include "iupac_pattern.h"
 #include "motif_score.h"
+#include "motif_centrality.h"
 #include "motif_sites.h"
 #include "peng.h"
 
@@ -103,9 +104,9 @@ int main(int nargs, char** args) {
   clock.lap("process (count, sweep, hill-climb, PWMs, EM, merging)");
   peng.filter_redundancy(Global::mergeBitfactorThreshold, result);
   std::vector<MotifScore> scores;
-  // (the scoring and the sites share one scan layout of the input)
+  // (the scoring, the sites and the centrality share one scan layout of the input)
   std::unique_ptr<ScanInput> scan;
-  if (Global::scoreMotifs || Global::sitesFilename) {
+  if (Global::scoreMotifs || Global::sitesFilename || Global::centralityFilename) {
     scan.reset(new ScanInput);
     build_scan_input(*Global::inputSequenceSet, scan.get());
   }
@@ -128,13 +129,19 @@ int main(int nargs, char** args) {
     clock.lap("score");
   }
   const std::vector<MotifScore>* sc = Global::scoreMotifs ? &scores : nullptr;
+  // the MEME file's order: as it is, or as the writers sort it (the same sort of the same vector: the same order)
+  std::vector<IUPACPattern*> meme_order(result);
+  if (!sc && (Global::sitesFilename || Global::centralityFilename))
+    std::sort(meme_order.begin(), meme_order.end(), sort_IUPAC_patterns);
   if (Global::sitesFilename) {
-    // the MEME file's order: as it is, or as the writers sort it (the same sort of the same vector: the same order)
-    std::vector<IUPACPattern*> order(result);
-    if (!sc) std::sort(order.begin(), order.end(), sort_IUPAC_patterns);
-    write_motif_sites(order, *Global::inputSequenceSet, *scan, *bgModel, Global::strand == Strand::BOTH_STRANDS,
+    write_motif_sites(meme_order, *Global::inputSequenceSet, *scan, *bgModel, Global::strand == Strand::BOTH_STRANDS,
                       Global::sitesPvalue, Global::sitesFilename);
     clock.lap("sites");
+  }
+  if (Global::centralityFilename) {
+    write_motif_centrality(meme_order, *Global::inputSequenceSet, *scan, *bgModel, Global::strand == Strand::BOTH_STRANDS,
+                           Global::centralityPvalue, Global::centralityFilename);
+    clock.lap("centrality");
   }
   scan.reset();
   if (pengk_host::rank() == 0) {
