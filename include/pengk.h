@@ -452,6 +452,33 @@ int pengk_centrality_summary(const uint64_t* h_hist_offsets, const uint64_t* h_h
 /* Pure CPU.  log10 P(X >= k), X ~ Binomial(n, p), k <= n, 0 <= p <= 1: the tail pengk_centrality_summary uses. */
 int pengk_binomial_log10_sf(uint64_t n, uint64_t k, double p, double* out);
 
+/* ---- motif refinement (--refine: the found motifs re-estimated and extended from their sites, as MEME, HOMER and STREME
+ *      end) -------------------------------------------------------------------------------------------
+ * Over the scan layout and the best sites of pengk_motif_best_sites.  Integer up to the counts: any slicing, any rank
+ * count and a numpy restatement give the same counts; the new matrix is a fixed double-precision formula on them.
+ * Both calls clamp the flank per motif: F = min(flank, (PENGK_MAX_MOTIF_LEN - w) / 2), so that w + 2F <=
+ * PENGK_MAX_MOTIF_LEN. */
+/* Site profiles.  For every motif m (width w = h_len[m], F as above) and every sequence i with a best site (d_best[m *
+ * n_seq + i] not PENGK_SCORE_SENTINEL and >= h_thr[m], d_site[m * n_seq + i] = 2p + s with p + w <= d_lens[i]), and every
+ * column c in [-F, w + F): the base at that column of the site read on the site's strand -- position p + c on +,
+ * position p + w - 1 - c complemented on - -- ADDS 1 to d_counts[(m * PENGK_MAX_MOTIF_LEN + c + F) * 5 + b], b = 0..3 for
+ * A, C, G, T and b = 4 where the position lies outside the sequence or holds another letter.  d_counts: n_motifs x
+ * PENGK_MAX_MOTIF_LEN x 5 uint64, caller-zeroed, accumulating (slices and shards add up; rows from w + 2F on stay
+ * untouched).  d_valid = NULL: every base of a sequence is valid.  flank >= 0. */
+int pengk_site_profiles(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_valid, const int64_t* d_offs,
+                        const uint32_t* d_lens, uint64_t n_seq, int n_motifs, const int32_t* d_best, const uint64_t* d_site,
+                        const int32_t* h_len, const int32_t* h_thr, int flank, uint64_t* d_counts);
+/* Pure CPU.  One motif's new matrix from its counts (h_counts: the motif's (w + 2F) x 5 rows of d_counts, summed over
+ * the ranks), in double, in this order: per column c = 0 .. w + 2F - 1, n = ((k[0] + k[1]) + k[2]) + k[3] (integers); for
+ * b = 0, 1, 2, 3 in this order q[c][b] = ((double)k[b] + bg[b]) / ((double)n + 1.0) (bg = h_bg taken as double, all > 0: one
+ * pseudocount spread by the background) and IC[c] = sum from 0.0 of q[c][b] * log2(q[c][b] / bg[b]).  The kept range
+ * [*first_out, *last_out) runs from the first to the last column with IC >= min_ic (0, 0 when there is none).  h_q ((w +
+ * 2F) x 4) and h_ic (w + 2F) receive every column's q and IC, h_pwm (up to PENGK_MAX_MOTIF_LEN x 4) the kept columns'
+ * q rounded to float, from row 0 on; sites_out the sequences that had a site (the five bins of column F).  Any of h_q,
+ * h_ic, h_pwm, sites_out may be NULL. */
+int pengk_profile_refine(const uint64_t* h_counts, int w, int flank, const float* h_bg, double min_ic, double* h_q,
+                         double* h_ic, float* h_pwm, int32_t* first_out, int32_t* last_out, uint64_t* sites_out);
+
 /* Self-test of the division sequence the serial EM's weights kernel uses where a PWM's operand ranges allow (the IEEE
  * division's instructions without its range scaling: csrc/em.hip, lean_div; src/peng.cpp:124-125, 186 are the three
  * divisions of a weight).  4096 x 256 threads draw pairs_per_thread random operand pairs each, keep those inside the

@@ -35,6 +35,7 @@ EXPORTS = [
     "pengk_motif_scan", "pengk_score_histograms", "pengk_score_summary",
     "pengk_score_tail_pvalues", "pengk_score_threshold", "pengk_sites_count", "pengk_sites_slices", "pengk_sites_emit",
     "pengk_motif_best_sites", "pengk_centrality_histograms", "pengk_centrality_summary", "pengk_binomial_log10_sf",
+    "pengk_site_profiles", "pengk_profile_refine",
 ]
 MAX_MOTIF_LEN = 64
 SCORE_SENTINEL = -2 ** 31
@@ -148,6 +149,9 @@ def lib():
         L.pengk_centrality_histograms.argtypes = [vp, C.c_int, vp, vp, vp, u64, vp, vp, C.c_uint32, vp, vp]
         L.pengk_centrality_summary.argtypes = [vp, vp, C.c_uint32, C.c_int, C.c_int, C.POINTER(CentralityStruct)]
         L.pengk_binomial_log10_sf.argtypes = [u64, u64, C.c_double, C.POINTER(C.c_double)]
+        L.pengk_site_profiles.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, vp, vp, vp, vp, C.c_int, vp]
+        L.pengk_profile_refine.argtypes = [vp, C.c_int, C.c_int, vp, C.c_double, vp, vp, vp, C.POINTER(C.c_int32),
+                                           C.POINTER(C.c_int32), C.POINTER(u64)]
         _lib = L
     return _lib
 
@@ -244,6 +248,29 @@ def binomial_log10_sf(n, k, p):
     out = C.c_double()
     _check(lib().pengk_binomial_log10_sf(int(n), int(k), float(p), C.byref(out)))
     return out.value
+
+
+def clamp_flank(w, flank):
+    """the flank a motif of width w gets: w + 2F <= MAX_MOTIF_LEN (pengk_site_profiles, pengk_profile_refine)"""
+    return min(int(flank), (MAX_MOTIF_LEN - int(w)) // 2)
+
+
+def profile_refine(counts, w, flank, bg, min_ic):
+    """one motif's new matrix from its site-profile counts (pengk_profile_refine, CPU); counts: at least (w + 2F) x 5
+    uint64 rows.  A dict: q (w + 2F x 4 double), ic, first, last (the kept columns [first, last)), pwm (the kept columns
+    as float32) and sites"""
+    F = clamp_flank(w, flank)
+    n = w + 2 * F
+    k = np.ascontiguousarray(np.asarray(counts, np.uint64).reshape(-1, 5)[:n])
+    assert len(k) == n
+    b = np.ascontiguousarray(bg, np.float32)
+    q, ic = np.zeros((n, 4), np.float64), np.zeros(n, np.float64)
+    pwm = np.zeros((MAX_MOTIF_LEN, 4), np.float32)
+    first, last, sites = C.c_int32(), C.c_int32(), C.c_uint64()
+    _check(lib().pengk_profile_refine(k.ctypes.data, w, int(flank), b.ctypes.data, float(min_ic), q.ctypes.data, ic.ctypes.data,
+                                      pwm.ctypes.data, C.byref(first), C.byref(last), C.byref(sites)))
+    return {"q": q, "ic": ic, "first": first.value, "last": last.value, "pwm": pwm[:last.value - first.value].copy(),
+            "sites": sites.value}
 
 
 def _pad_motifs(S, lens):
@@ -595,6 +622,19 @@ class Context:
         _check(lib().pengk_centrality_histograms(self.h, n, _ptr(best), _ptr(site), _ptr(lens_dev), n_seq, w.ctypes.data,
                                                  th.ctypes.data, max_len, _ptr(hd), _ptr(hl)))
         return hd, hl
+
+    # ---- motif refinement (--refine) ---------------------------------------------------------------------------
+    def site_profiles(self, scan, best, site, widths, thr, flank, counts=None):
+        """device uint64 n_motifs x MAX_MOTIF_LEN x 5: the base counts of every column in [-F, w + F) of the best sites
+        (best, site from motif_best_sites on the same scan) at or above thr, ADDED to counts (allocated zeroed if None)"""
+        n = len(widths)
+        w = np.ascontiguousarray(widths, np.int32)
+        th = np.ascontiguousarray(thr, np.int32)
+        if counts is None:
+            counts = self.to_device(np.zeros((max(n, 1), MAX_MOTIF_LEN, 5), np.uint64))
+        _check(lib().pengk_site_profiles(self.h, _ptr(scan[0]), _ptr(scan[1]), _ptr(scan[2]), _ptr(scan[3]), scan[4], n, _ptr(best),
+                                         _ptr(site), w.ctypes.data, th.ctypes.data, int(flank), _ptr(counts)))
+        return counts
 
     def em_device(self, W, n_pwm, d_pwms, counts, bg, d_state, d_change, saturation=1e4, threshold=0.08, max_iterations=10):
         _check(lib().pengk_em_device(self.h, W, n_pwm, _ptr(d_pwms), saturation, threshold, max_iterations, _ptr(counts),

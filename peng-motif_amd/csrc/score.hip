@@ -586,6 +586,103 @@ __global__ __launch_bounds__(HIST_THREADS) void centrality_hist_kernel(const int
   }
 }
 
+// ---- site profiles (pengk_site_profiles) -------------------------------------------------------------
+constexpr int PROF_THREADS = 256;
+constexpr int PROF_BINS = PENGK_MAX_MOTIF_LEN * 5;
+
+// per motif (blockIdx.y): the base of every column c in [-F, w + F) of the best sites at or above the motif's threshold,
+// read on the site's strand, ADDED to counts[(m * PENGK_MAX_MOTIF_LEN + c + F) * 5 + b] (b = 4: outside the sequence or
+// not A/C/G/T).  A wave takes 64 consecutive sequences.  For a strong motif nearly every lane of it adds to the same
+// (column, base) bin, so the lanes do not add at all: per column the wave ballots the two bits of the base, "is a base"
+// and "has a site", counts the five bins from the masks, and lanes 0..4 add them once to the block's LDS bins, which
+// are flushed once per block.  A site with its flanks spans at most 64 bases: three words per lane, loaded once.
+// A wave without a site (the usual wave of a weak motif) reads best, site and length and goes on.
+__global__ __launch_bounds__(PROF_THREADS) void site_profile_kernel(const uint64_t* __restrict__ words,
+                                                                    const uint32_t* __restrict__ valid,
+                                                                    const int64_t* __restrict__ offs,
+                                                                    const uint32_t* __restrict__ lens, uint64_t n_seq,
+                                                                    const int32_t* __restrict__ best,
+                                                                    const unsigned long long* __restrict__ site,
+                                                                    const int32_t* __restrict__ wtf,
+                                                                    unsigned long long* __restrict__ counts) {
+  __shared__ uint32_t bins[PROF_BINS];
+  const int m = blockIdx.y;
+  const int32_t w = wtf[3 * m], t = wtf[3 * m + 1], F = wtf[3 * m + 2];
+  const int32_t C = w + 2 * F;  // <= PENGK_MAX_MOTIF_LEN (the host clamps F)
+  for (int k = threadIdx.x; k < PROF_BINS; k += PROF_THREADS) bins[k] = 0;
+  __syncthreads();
+  const int32_t* B = best + (uint64_t)m * n_seq;
+  const unsigned long long* S = site + (uint64_t)m * n_seq;
+  const int lane = threadIdx.x & 63;
+  // (every lane of a wave makes the same trips: the ballots below see the whole wave)
+  for (uint64_t i0 = blockIdx.x * (uint64_t)PROF_THREADS + (threadIdx.x & ~63); i0 < n_seq;
+       i0 += (uint64_t)gridDim.x * PROF_THREADS) {
+    const uint64_t i = i0 + lane;
+    bool sel = false;
+    int64_t L = 0, p = 0;
+    int32_t strand = 0;
+    if (i < n_seq) {
+      const int32_t b = B[i];
+      L = lens[i];
+      if (b != PENGK_SCORE_SENTINEL && b >= t && L >= w) {
+        const uint64_t c = S[i];
+        p = (int64_t)(c >> 1);
+        strand = (int32_t)(c & 1);
+        sel = p <= L - w;  // (not a window of this sequence: no site)
+      }
+    }
+    const unsigned long long has = __ballot(sel);
+    if (has == 0) continue;
+    // the bases [g0, g0 + C) of the sequence that lie inside it: [a, e), in the words j0 .. j0 + 2 of the sequence
+    const int64_t g0 = p - F;
+    int64_t a = 0, e = 0, j0 = 0;
+    uint64_t W0 = 0, W1 = 0, W2 = 0;
+    uint32_t V0 = 0, V1 = 0, V2 = 0;
+    if (sel) {
+      a = g0 > 0 ? g0 : 0;
+      e = g0 + C < L ? g0 + C : L;  // a <= p < p + w <= e
+      j0 = a >> 5;
+      const int64_t j1 = (e - 1) >> 5;  // <= j0 + 2: e - a <= 64
+      const uint64_t w0 = ((uint64_t)offs[i] >> 5) + (uint64_t)j0;
+      W0 = words[w0];
+      V0 = valid ? valid[w0] : 0xFFFFFFFFu;
+      if (j0 + 1 <= j1) {
+        W1 = words[w0 + 1];
+        V1 = valid ? valid[w0 + 1] : 0xFFFFFFFFu;
+      }
+      if (j0 + 2 <= j1) {
+        W2 = words[w0 + 2];
+        V2 = valid ? valid[w0 + 2] : 0xFFFFFFFFu;
+      }
+    }
+    for (int32_t c = 0; c < C; ++c) {
+      // column c of the site: base g0 + c on +, g0 + C - 1 - c complemented on -
+      const int64_t q = g0 + (strand ? C - 1 - c : c);
+      bool ok = false;
+      uint32_t b = 0;
+      if (sel && q >= a && q < e) {
+        const int64_t j = (q >> 5) - j0;
+        const uint64_t W = j == 0 ? W0 : (j == 1 ? W1 : W2);
+        const uint32_t V = j == 0 ? V0 : (j == 1 ? V1 : V2);
+        const uint32_t r = (uint32_t)q & 31u;
+        ok = (V >> r) & 1u;
+        b = ((uint32_t)(W >> (2 * r)) & 3u) ^ (strand ? 3u : 0u);
+      }
+      const unsigned long long mo = __ballot(ok), m0 = __ballot(b & 1u), m1 = __ballot(b & 2u);
+      if (lane < 5) {
+        const unsigned long long mask =
+            lane == 4 ? has & ~mo : mo & (lane & 1 ? m0 : ~m0) & (lane & 2 ? m1 : ~m1);
+        const uint32_t n = (uint32_t)__popcll(mask);
+        if (n) atomicAdd(&bins[c * 5 + lane], n);
+      }
+    }
+  }
+  __syncthreads();
+  unsigned long long* out = counts + (uint64_t)m * PROF_BINS;
+  for (int k = threadIdx.x; k < C * 5; k += PROF_THREADS)
+    if (bins[k]) atomicAdd(&out[k], (unsigned long long)bins[k]);
+}
+
 int grid_for(pengk_ctx* ctx, uint64_t work, uint32_t per_block, uint32_t per_cu) {
   const uint64_t need = (work + per_block - 1) / per_block;
   const uint64_t cap = (uint64_t)ctx->num_cu * per_cu;
@@ -1218,6 +1315,79 @@ int pengk_centrality_summary(const uint64_t* h_hist_offsets, const uint64_t* h_h
     }
   }
   out->log10_evalue = out->log10_pvalue + std::log10((double)(Dm + 1)) + std::log10((double)n_motifs);
+  return PENGK_OK;
+}
+
+int pengk_site_profiles(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_valid, const int64_t* d_offs,
+                        const uint32_t* d_lens, uint64_t n_seq, int n_motifs, const int32_t* d_best, const uint64_t* d_site,
+                        const int32_t* h_len, const int32_t* h_thr, int flank, uint64_t* d_counts) {
+  if (!ctx || n_motifs < 0 || flank < 0 || (n_motifs && (!h_len || !h_thr || !d_counts)) ||
+      (n_seq && n_motifs && (!d_words || !d_offs || !d_lens || !d_best || !d_site)))
+    return fail(PENGK_ERR_ARG, "pengk_site_profiles: bad argument");
+  for (int m = 0; m < n_motifs; ++m)
+    if (h_len[m] < 1 || h_len[m] > PENGK_MAX_MOTIF_LEN)
+      return fail(PENGK_ERR_ARG, "pengk_site_profiles: motif %d has width %d (1..%d)", m, h_len[m], PENGK_MAX_MOTIF_LEN);
+  SCORE_ENTER(ctx);
+  if (n_seq == 0 || n_motifs == 0) return PENGK_OK;
+  std::vector<int32_t> wtf(3 * (size_t)n_motifs);
+  for (int m = 0; m < n_motifs; ++m) {
+    wtf[3 * m] = h_len[m];
+    wtf[3 * m + 1] = h_thr[m];
+    wtf[3 * m + 2] = std::min(flank, (PENGK_MAX_MOTIF_LEN - h_len[m]) / 2);
+  }
+  int rc = ensure_scratch(ctx, &ctx->d_misc, &ctx->misc_bytes, wtf.size() * sizeof(int32_t));
+  if (rc) return rc;
+  PENGK_HIP(hipStreamSynchronize(ctx->stream));
+  PENGK_HIP(hipMemcpy(ctx->d_misc, wtf.data(), wtf.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  // blocks per motif: enough to fill the device, and so many that a block's 32-bit LDS bins cannot wrap (< 2^31 each)
+  const uint64_t need = (n_seq + PROF_THREADS - 1) / PROF_THREADS;
+  const uint64_t fill = (uint64_t)ctx->num_cu * 8 / (uint64_t)n_motifs + 1;
+  const uint64_t per_motif = std::max<uint64_t>(std::min(need, fill), (n_seq >> 31) + 1);
+  const dim3 grid((unsigned)per_motif, (unsigned)n_motifs);
+  hipLaunchKernelGGL(site_profile_kernel, grid, dim3(PROF_THREADS), 0, ctx->stream, d_words, d_valid, d_offs, d_lens, n_seq,
+                     d_best, (const unsigned long long*)d_site, (const int32_t*)ctx->d_misc, (unsigned long long*)d_counts);
+  PENGK_HIP(hipGetLastError());
+  return PENGK_OK;
+}
+
+int pengk_profile_refine(const uint64_t* h_counts, int w, int flank, const float* h_bg, double min_ic, double* h_q,
+                         double* h_ic, float* h_pwm, int32_t* first_out, int32_t* last_out, uint64_t* sites_out) {
+  if (!h_counts || !h_bg || !first_out || !last_out || w < 1 || w > PENGK_MAX_MOTIF_LEN || flank < 0 || !(min_ic == min_ic))
+    return fail(PENGK_ERR_ARG, "pengk_profile_refine: bad argument");
+  for (int b = 0; b < 4; ++b)
+    if (!(h_bg[b] > 0.0f)) return fail(PENGK_ERR_ARG, "pengk_profile_refine: background frequency %d is not positive", b);
+  const int F = std::min(flank, (PENGK_MAX_MOTIF_LEN - w) / 2), C = w + 2 * F;
+  int first = C, last = 0;  // [first, last): empty
+  for (int c = 0; c < C; ++c) {
+    const uint64_t* k = h_counts + (size_t)c * 5;
+    const uint64_t n = ((k[0] + k[1]) + k[2]) + k[3];
+    double ic = 0.0;
+    for (int b = 0; b < 4; ++b) {
+      const double g = (double)h_bg[b];
+      const double q = ((double)k[b] + g) / ((double)n + 1.0);
+      ic += q * std::log2(q / g);
+      if (h_q) h_q[(size_t)c * 4 + b] = q;
+    }
+    if (h_ic) h_ic[c] = ic;
+    if (ic >= min_ic) {
+      if (first == C) first = c;
+      last = c + 1;
+    }
+  }
+  if (first == C) first = 0;
+  if (h_pwm)
+    for (int c = first; c < last; ++c) {
+      const uint64_t* k = h_counts + (size_t)c * 5;
+      const uint64_t n = ((k[0] + k[1]) + k[2]) + k[3];
+      for (int b = 0; b < 4; ++b)
+        h_pwm[(size_t)(c - first) * 4 + b] = (float)(((double)k[b] + (double)h_bg[b]) / ((double)n + 1.0));
+    }
+  *first_out = first;
+  *last_out = last;
+  if (sites_out) {  // every site adds 1 to one bin of every column: the first motif column's total
+    const uint64_t* k = h_counts + (size_t)F * 5;
+    *sites_out = k[0] + k[1] + k[2] + k[3] + k[4];
+  }
   return PENGK_OK;
 }
 

@@ -48,14 +48,19 @@ char* Global::sitesFilename = nullptr;
 double Global::sitesPvalue = 1e-4;
 char* Global::centralityFilename = nullptr;
 double Global::centralityPvalue = 1e-4;
+char* Global::refineFilename = nullptr;
+double Global::refinePvalue = 1e-4;
+int Global::refineFlank = 8;
+int Global::refineIterations = 3;
+double Global::refineMinIC = 0.25;
 
 void Global::init(int nargs, char* args[]) {
   readArguments(nargs, args);
   Alphabet::init(alphabetType);
   pengk_host::start_context();  // the device runtime starts while the FASTA files are read
   pengk_host::start_sharded_ingest();  // multi-GPU run: every rank reads its own byte range of the files
-  // (the scoring, the sites and the centrality scan the input after the motifs are found)
-  pengk_host::keep_host_codes(scoreMotifs || sitesFilename || centralityFilename);
+  // (the scoring, the sites, the centrality and the refinement scan the input after the motifs are found)
+  pengk_host::keep_host_codes(scoreMotifs || sitesFilename || centralityFilename || refineFilename);
   // both strands are handled inside the count; sequences are always read single stranded
   // ... and every chunk of the input set is packed and sent to the device while the rest is still being read
   pengk_host::begin_streaming_pack(patternLength);
@@ -219,6 +224,37 @@ void Global::readArguments(int nargs, char* args[]) {
         log_line("ERROR", "--centrality-pvalue must be a number in (0, 1]");
         exit(4);
       }
+    } else if (!strcmp(a, "--refine")) {
+      refineFilename = (char*)need(i, nargs, args, printHelp);
+    } else if (!strcmp(a, "--refine-pvalue")) {
+      const char* v = need(i, nargs, args, printHelp);
+      char* end = nullptr;
+      refinePvalue = std::strtod(v, &end);
+      if (end == v || *end || !(refinePvalue > 0.0 && refinePvalue <= 1.0)) {
+        printHelp();
+        log_line("ERROR", "--refine-pvalue must be a number in (0, 1]");
+        exit(4);
+      }
+    } else if (!strcmp(a, "--refine-flank") || !strcmp(a, "--refine-iterations")) {
+      const bool flank = a[9] == 'f';
+      const char* v = need(i, nargs, args, printHelp);
+      char* end = nullptr;
+      const long n = std::strtol(v, &end, 10);
+      if (end == v || *end || n < (flank ? 0 : 1) || n > 1000) {
+        printHelp();
+        log_line("ERROR", flank ? "--refine-flank must be an integer in [0, 1000]" : "--refine-iterations must be an integer in [1, 1000]");
+        exit(4);
+      }
+      (flank ? refineFlank : refineIterations) = (int)n;
+    } else if (!strcmp(a, "--refine-min-ic")) {
+      const char* v = need(i, nargs, args, printHelp);
+      char* end = nullptr;
+      refineMinIC = std::strtod(v, &end);
+      if (end == v || *end || !(refineMinIC >= 0.0 && refineMinIC <= 2.0)) {
+        printHelp();
+        log_line("ERROR", "--refine-min-ic must be a number of bits in [0, 2]");
+        exit(4);
+      }
     } else if (!strcmp(a, "--version")) {
       std::cout << "peng_motif " << VERSION_NUMBER << std::endl;  // (src/Global.cpp:299-301: without the word)
       exit(0);
@@ -267,6 +303,12 @@ void Global::printHelp() {
   printf("  --centrality FILE              test every motif for enrichment at the sequence centres (TSV: best site\n");
   printf("                                 per sequence at p-value --centrality-pvalue or below, binomial test)\n");
   printf("  --centrality-pvalue FLOAT      p-value threshold of a best site, in (0, 1] (default 1e-4)\n");
+  printf("  --refine FILE                  re-estimate every motif from its best site per sequence, flanks included,\n");
+  printf("                                 and write the refined motifs (MEME) to FILE\n");
+  printf("  --refine-pvalue FLOAT          p-value threshold of a best site, in (0, 1] (default 1e-4)\n");
+  printf("  --refine-flank INT             columns looked at on either side of a motif (default 8)\n");
+  printf("  --refine-iterations INT        at most this many rounds of sites -> matrix (default 3)\n");
+  printf("  --refine-min-ic FLOAT          information (bits) an outermost kept column needs (default 0.25)\n");
   printf("  --threads INT                  accepted for compatibility\n");
   printf("  --device INT                   HIP device index (default 0)\n");
   printf("  -v INT                         verbosity\n");

@@ -63,6 +63,11 @@ class Global {
   static double sitesPvalue;                 // --sites-pvalue
   static char* centralityFilename;           // --centrality (new: central enrichment of the motifs)
   static double centralityPvalue;            // --centrality-pvalue
+  static char* refineFilename;               // --refine (new: the motifs re-estimated from their sites)
+  static double refinePvalue;                // --refine-pvalue
+  static int refineFlank;                    // --refine-flank
+  static int refineIterations;               // --refine-iterations
+  static double refineMinIC;                 // --refine-min-ic
 
   static void init(int nargs, char* args[]);
   static void destruct();

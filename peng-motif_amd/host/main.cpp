@@ -15,6 +15,7 @@
 #include "iupac_pattern.h"
 #include "motif_score.h"
 #include "motif_centrality.h"
+#include "motif_refine.h"
 #include "motif_sites.h"
 #include "peng.h"
 
@@ -104,9 +105,9 @@ int main(int nargs, char** args) {
   clock.lap("process (count, sweep, hill-climb, PWMs, EM, merging)");
   peng.filter_redundancy(Global::mergeBitfactorThreshold, result);
   std::vector<MotifScore> scores;
-  // (the scoring, the sites and the centrality share one scan layout of the input)
+  // (the scoring, the sites, the centrality and the refinement share one scan layout of the input)
   std::unique_ptr<ScanInput> scan;
-  if (Global::scoreMotifs || Global::sitesFilename || Global::centralityFilename) {
+  if (Global::scoreMotifs || Global::sitesFilename || Global::centralityFilename || Global::refineFilename) {
     scan.reset(new ScanInput);
     build_scan_input(*Global::inputSequenceSet, scan.get());
   }
@@ -131,7 +132,7 @@ int main(int nargs, char** args) {
   const std::vector<MotifScore>* sc = Global::scoreMotifs ? &scores : nullptr;
   // the MEME file's order: as it is, or as the writers sort it (the same sort of the same vector: the same order)
   std::vector<IUPACPattern*> meme_order(result);
-  if (!sc && (Global::sitesFilename || Global::centralityFilename))
+  if (!sc && (Global::sitesFilename || Global::centralityFilename || Global::refineFilename))
     std::sort(meme_order.begin(), meme_order.end(), sort_IUPAC_patterns);
   if (Global::sitesFilename) {
     write_motif_sites(meme_order, *Global::inputSequenceSet, *scan, *bgModel, Global::strand == Strand::BOTH_STRANDS,
@@ -142,6 +143,16 @@ int main(int nargs, char** args) {
     write_motif_centrality(meme_order, *Global::inputSequenceSet, *scan, *bgModel, Global::strand == Strand::BOTH_STRANDS,
                            Global::centralityPvalue, Global::centralityFilename);
     clock.lap("centrality");
+  }
+  if (Global::refineFilename) {
+    RefineSettings rs;
+    rs.pvalue = Global::refinePvalue;
+    rs.flank = Global::refineFlank;
+    rs.iterations = Global::refineIterations;
+    rs.min_ic = Global::refineMinIC;
+    write_refined_motifs(meme_order, *Global::inputSequenceSet, *scan, *bgModel, Global::strand == Strand::BOTH_STRANDS, rs,
+                         Global::refineFilename);
+    clock.lap("refine");
   }
   scan.reset();
   if (pengk_host::rank() == 0) {

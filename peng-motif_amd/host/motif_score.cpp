@@ -7,12 +7,10 @@
 
 #include "device.h"
 
-namespace {
 int32_t log_odds(float p, float b) {
   const double v = 100.0 * std::log2((double)p / (double)b);  // (p = 0: -inf)
   return (int32_t)std::lround(std::max(-2000.0, std::min(2000.0, v)));
 }
-}  // namespace
 
 void motif_log_odds(const std::vector<IUPACPattern*>& pats, const float* bg0, std::vector<int32_t>& S, std::vector<int32_t>& len,
                     const char* who) {

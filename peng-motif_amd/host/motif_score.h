@@ -26,6 +26,8 @@ struct ScanInput {
 };
 void build_scan_input(SequenceSet& set, ScanInput* in);
 
+// one entry of the integer log-odds: clamp(lround(100 log2(p / b)), -2000, 2000)
+int32_t log_odds(float p, float b);
 // S[(m * PENGK_MAX_MOTIF_LEN + j) * 4 + a] = clamp(lround(100 log2(pwm / bg0)), -2000, 2000) and len[m] of every motif
 // (a motif wider than PENGK_MAX_MOTIF_LEN ends the program; `who` names the step in the message)
 void motif_log_odds(const std::vector<IUPACPattern*>& pats, const float* bg0, std::vector<int32_t>& S, std::vector<int32_t>& len,
