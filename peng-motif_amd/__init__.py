@@ -565,6 +565,14 @@ class Context:
                                       Sp.ctypes.data, ln.ctypes.data, int(both), th.ctypes.data, _ptr(counts), i0, i1,
                                       _ptr(out) if out is not None else None, cap))
 
+    def sites_records(self, scan, S, lens, both, thr, counts, i0, i1, n_records, buf=None):
+        """the n_records pengk_site records of sequences [i0, i1) as pengk_sites_emit wrote them (a SITE array: motif,
+        then sequence within the slice, then position, + before -; not regrouped); buf: a device buffer to reuse"""
+        if buf is None or buf.nbytes < max(n_records, 1) * SITE.itemsize:
+            buf = self.empty(max(n_records, 1) * SITE.itemsize, np.uint8)
+        self.sites_emit(scan, S, lens, both, thr, counts, i0, i1, buf, n_records)
+        return buf.to_host()[:n_records * SITE.itemsize].view(SITE).copy()
+
     def motif_sites(self, scan, S, lens, both, thr):
         """every site, in the --sites order (motif, global sequence, position, + before -): a SITE array whose seq field
         is the global sequence index (uint64 here), plus the count pass's per-motif totals"""
