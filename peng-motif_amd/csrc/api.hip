@@ -512,14 +512,13 @@ int pengk_seed_candidates(pengk_ctx* ctx, int W, const float* d_z, const uint32_
   if (capacity < 0 || capacity > (int64_t)1 << 28) return fail(PENGK_ERR_ARG, "pengk_seed_candidates: capacity out of range");
   PENGK_ENTER(ctx);
   const uint32_t cap = (uint32_t)capacity;
-  const uint32_t cthr = count_threshold > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)count_threshold;
   const size_t need = 256 + (size_t)cap * 8;
   int rc = ensure_scratch(ctx, &ctx->d_misc, &ctx->misc_bytes, need);
   if (rc) return rc;
   uint32_t* d_n = (uint32_t*)ctx->d_misc;
   uint32_t* d_ids = (uint32_t*)((char*)ctx->d_misc + 256);
   float* d_zs = (float*)(d_ids + cap);
-  rc = launch_seed_candidates(ctx, W, d_z, d_counts, z_threshold, cthr, cap, d_n, d_ids, d_zs);
+  rc = launch_seed_candidates(ctx, W, d_z, d_counts, z_threshold, count_threshold, cap, d_n, d_ids, d_zs);
   if (rc) return rc;
   uint32_t n = 0;
   PENGK_HIP(hipMemcpyAsync(&n, d_n, sizeof n, hipMemcpyDeviceToHost, ctx->stream));

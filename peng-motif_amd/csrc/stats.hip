@@ -54,7 +54,7 @@ __device__ __forceinline__ void pattern_statistics(float pk, float fl, uint32_t 
     lp = __builtin_inff();
   } else {
     const float fn = (float)n;
-    const float frac = (float)(1.0 - (double)(mu / (float)(n + 1u)));
+    const float frac = (float)(1.0 - (double)(mu / (float)((unsigned long long)n + 1ull)));  // (the reference adds the 1 to a size_t: n = 2^32 - 1 must not wrap)
     if (fn > mu && n > 5u) {
       const double dn = (double)n;
       lp = (float)(dn * log((double)(mu / fn)) + dn - (double)mu - 0.5 * log(6.283 * dn * (double)frac * (double)frac));
@@ -262,14 +262,16 @@ int launch_w(pengk_ctx* ctx, int both, int k, int max_k, const float* d_V, const
 // count >= threshold can become seeds.  This kernel compacts exactly those (id, z) pairs: wave ballot, one atomic per
 // wave.  Order of the list is arbitrary; the caller sorts the few thousand survivors.
 __global__ __launch_bounds__(256) void seed_candidates_kernel(const float* __restrict__ z, const uint32_t* __restrict__ counts,
-                                                              uint32_t np, float z_threshold, uint32_t count_threshold,
+                                                              uint32_t np, float z_threshold, unsigned long long count_threshold,
                                                               uint32_t cap, uint32_t* __restrict__ n_out,
                                                               uint32_t* __restrict__ ids, float* __restrict__ zs) {
   const uint32_t lane = threadIdx.x & 63u;
   for (uint32_t base = (blockIdx.x * blockDim.x + threadIdx.x) & ~63u; base < np; base += gridDim.x * blockDim.x) {
     const uint32_t x = base + lane;
     const float zx = x < np ? z[x] : 0.0f;
-    const bool keep = x < np && !(zx < z_threshold) && counts[x] >= count_threshold;
+    // z >= threshold: a NaN z is no candidate (the reference's walk stops at it); the count is compared in 64 bits, so that a
+    // threshold above 2^32 - 1 admits no bin, as the reference's `counts[x] < count_thr` on size_t does
+    const bool keep = x < np && zx >= z_threshold && (unsigned long long)counts[x] >= count_threshold;
     const unsigned long long m = __builtin_amdgcn_ballot_w64(keep);
     if (m == 0) continue;
     uint32_t first = 0;
@@ -288,12 +290,12 @@ __global__ __launch_bounds__(256) void seed_candidates_kernel(const float* __res
 }  // namespace
 
 int launch_seed_candidates(pengk_ctx* ctx, int W, const float* d_z, const uint32_t* d_counts, float z_threshold,
-                           uint32_t count_threshold, uint32_t cap, uint32_t* d_n, uint32_t* d_ids, float* d_zs) {
+                           uint64_t count_threshold, uint32_t cap, uint32_t* d_n, uint32_t* d_ids, float* d_zs) {
   const uint32_t np = 1u << (2 * W);
   PENGK_HIP(hipMemsetAsync(d_n, 0, sizeof(uint32_t), ctx->stream));
   const uint32_t need = (np + 255) / 256, lim = (uint32_t)ctx->num_cu * 8u;
   hipLaunchKernelGGL(seed_candidates_kernel, dim3(need < lim ? need : lim), dim3(256), 0, ctx->stream, d_z, d_counts, np,
-                     z_threshold, count_threshold, cap, d_n, d_ids, d_zs);
+                     z_threshold, (unsigned long long)count_threshold, cap, d_n, d_ids, d_zs);
   PENGK_HIP(hipGetLastError());
   return PENGK_OK;
 }

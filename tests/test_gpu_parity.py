@@ -13,6 +13,7 @@ import pytest
 
 import peng_motif_amd as pk
 from oracle import oracle as po
+from table_edges_model import _exact_S
 
 pytestmark = pytest.mark.gpu
 
@@ -1202,51 +1203,6 @@ def test_seed_candidates_on_device(ctx, golden_dir, name):
     canon = lambda x: min(x, po.revcomp(x, W)) if both else x  # noqa: E731
     ref_seeds = po.select(W, r["z"], r["counts"], zthr, cthr, not both, True)
     assert sorted(canon(x) for x in sel) == sorted(canon(int(x)) for x in ref_seeds)
-
-
-def _exact_S(p1, c1, s1, p2, c2, s2, both, bg):
-    """IUPACPattern::calculate_S restated with its float32 running sums (src/iupac_pattern.cpp:538-615)."""
-    f32, f64 = np.float32, np.float64
-    eps = f32(1e-4)
-
-    def term(x, y):
-        mean = f32(f32(f32(x + y) + f32(2) * eps) / f32(2))
-        return (f64(f32(x + eps)) * np.log2(f64(f32(x + eps))) + f64(f32(y + eps)) * np.log2(f64(f32(y + eps)))
-                - f64(f32(f32(2) * mean)) * np.log2(f64(mean)))
-
-    def d(a, b, oa, ob, n):
-        acc = f32(0)
-        for i in range(n):
-            for k in range(4):
-                acc = f32(f64(acc) + term(a[oa + i][k], b[ob + i][k]))
-        return acc
-
-    def dbg(a, oa, n):
-        acc = f32(0)
-        for i in range(n):
-            for k in range(4):
-                acc = f32(f64(acc) + term(a[oa + i][k], bg[k]))
-        return acc
-
-    big, small = (p1, c1, s1), (p2, c2, s2)
-    if len(p1) < len(p2):
-        big, small = small, big
-    lb, ls = len(big[0]), len(small[0])
-    best = -np.inf
-    for orient in range(2 if both else 1):
-        pb, ps = big[0], small[0]
-        if orient == 1:
-            if big[2] < small[2]:
-                pb = big[1]
-            else:
-                ps = small[1]
-        for shift in range(6 - ls, lb - 6 + 1):
-            off_s, off_b = -min(shift, 0), max(shift, 0)
-            ov = min(lb - off_b, ls - off_s)
-            sc = f32(0.5 * f64(f32(dbg(pb, off_b, ov) + dbg(ps, off_s, ov))) - f64(d(pb, ps, off_b, off_s, ov)))
-            if sc > best:
-                best = sc
-    return best
 
 
 @pytest.mark.parametrize("both", [True, False])
