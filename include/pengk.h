@@ -268,7 +268,11 @@ int pengk_iupac_aggregate(pengk_ctx* ctx, int W, int both_strands, const uint64_
  *   0  the reference's float32 terms (three divisions per k-mer weight), summed in fp64 through a fixed tree.
  *   1  (opt-in) the weight c*s / (1 + s/(prod/bg)) evaluated as c*s*prod / (prod + s*bg) with one
  *      reciprocal (~1 ulp per term), fp64 tree sums: the throughput mode, 2.3e12 PWM-k-mer evaluations/s.
- * Modes 0 and 1 agree with the reference within BASELINE.json's 1e-5 relative (the reference's own serial float32
+ *      Its domain: for every k-mer with a count, c*s*prod >= 2^-126 and prod + s*bg < 2^126 (prod = the float32
+ *      product over the PWM columns).  Nothing is promised outside it: a c*s*prod below 2^-150 is 0, and so is the term
+ *      where s*bg overflows, although the reference's weight may be an ordinary float there.  Modes 0 and 2 take the
+ *      reference's three divisions.
+ * Modes 0 and 1 (mode 1: on its domain) agree with the reference within BASELINE.json's 1e-5 relative (the reference's own serial float32
  * sums are off by up to 2.6e-4 relative from the exact ones); the float32 product over the PWM columns is built in
  * the reference's order in all modes.
  * max_iterations <= 0: no iteration (the reference's loop condition, src/peng.cpp:104), the PWMs come back unchanged.
