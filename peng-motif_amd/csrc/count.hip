@@ -13,8 +13,9 @@
 //
 // An item that continues a run (long sequences are split) first replays a 3W-3..-base prologue in
 // front of its first window.  If no window of the prologue is suppressed, the ring it leaves is
-// provably the true one (see DESIGN.md "non-overlap rule"); otherwise the item is pushed on a
-// defer list and redone by count_fixup_kernel, which searches backwards for a certified start.
+// provably the true one (see DESIGN.md "non-overlap rule"); otherwise -- or where the run has fewer
+// windows in front of the item than the prologue replays -- the item is pushed on a defer list and
+// redone by count_fixup_kernel, which searches backwards for a certified start.
 #include <stdlib.h>
 
 #include <type_traits>
@@ -203,7 +204,22 @@ __device__ __forceinline__ void scan_items(const uint32_t* __restrict__ words32,
     if (__any(cont ? 1 : 0)) {
       // full prologue: rebuild the ring of counted windows in front of a continuing item
       lo = words32[wi];
+      // The replay needs P - W + 1 windows of the item's own run in front of it.  The packer never cuts closer to the head
+      // of a run (every item in front of a continuing one has item_windows >= 64 of them: one step of this loop), but an
+      // item list attached by hand may: the replay would then take windows of whatever lies in front of the run for
+      // counted ones.  Such an item goes to the exact fallback, which starts at the head.
       bool dirty = false;
+      if (cont) {
+        uint32_t have = 0;
+        for (uint32_t j = it; j > 0 && have < (uint32_t)(G::P - W + 1);) {
+          const uint64_t prev = items[--j];
+          have += (uint32_t)((prev >> ITEM_NW_SHIFT) & ITEM_NW_MASK);
+          if (((prev >> ITEM_CONT_SHIFT) & 1ull) == 0) {
+            dirty = have < (uint32_t)(G::P - W + 1);
+            break;
+          }
+        }
+      }
 #pragma unroll
       for (int ch = 0; ch < G::P / 16; ++ch) {
         const uint32_t hi = words32[wi + 1];
@@ -971,7 +987,9 @@ __global__ __launch_bounds__(256) void mirror_kernel(uint32_t* __restrict__ hist
 // ---------------------------------------------------------------------------------------------
 // K1b: (k+1)-mer counts for inputs made of whole sequences.  Each item owns the bases
 // [ws, ws+nw) (+ the W-1 tail bases if it is the last item of its run); per base one 3-mer bin,
-// plus first-base / first-2-mer bins at the head of a run; n1 and n2 follow as marginals:
+// plus first-base / first-2-mer bins at the head of a run; a continuing item takes its two bases
+// of context from its own run only (one, if it starts on the run's second base); n1 and n2 follow
+// as marginals:
 //   n2[ab] = sum_c n3[cab] + #runs starting with ab,   n1[a] = sum_b n2[ba] + #runs starting with a.
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void bg_count_kernel(const uint32_t* __restrict__ words32,
@@ -994,7 +1012,16 @@ __global__ __launch_bounds__(256) void bg_count_kernel(const uint32_t* __restric
     uint32_t y = 0;
     uint32_t pos = 2;  // bases of context available in front of the current one (saturates at 2)
     if (cont) {
-      y = (base_at(words32, ws - 2) << 2) | base_at(words32, ws - 1);
+      // context only from the item's own run: a hand-built item list may begin its second item on the run's second
+      // base (the packer's items in front of a continuing one have item_windows >= 64 windows)
+      const uint64_t prev = items[it - 1];
+      const bool second = ((prev >> ITEM_CONT_SHIFT) & 1ull) == 0 && ((prev >> ITEM_NW_SHIFT) & ITEM_NW_MASK) == 1;
+      if (second) {
+        y = base_at(words32, ws - 1);
+        pos = 1;
+      } else {
+        y = (base_at(words32, ws - 2) << 2) | base_at(words32, ws - 1);
+      }
     } else {
       pos = 0;
     }

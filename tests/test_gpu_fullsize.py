@@ -9,6 +9,8 @@ since the oracle cannot finish these sizes in seconds:
     shows on a 200k-sequence sample of the same generator
   * mirror symmetry and idempotence; fused background counters == standalone K1b == closed form totals
   * the sweep is a pure function: bit-identical z on a second run; EM is deterministic run to run
+  * stream offsets above 2^32 bases (22M x 200 bp): the count of the whole is the sum of the counts of two halves that
+    each stay below 2^32
 """
 import numpy as np
 import pytest
@@ -63,6 +65,48 @@ def test_full_size_shard_additivity_and_ltot(ctx):
     assert 0 < frac_full < 1e-3 and abs(frac_full - frac_sample) < 0.25 * frac_sample + 1e-7
     # background counters: totals follow from the sequence geometry
     assert int(bg[:4].sum()) == n * L and int(bg[4:20].sum()) == n * (L - 1) and int(bg[20:].sum()) == n * (L - 2)
+
+
+def test_stream_offsets_above_2_to_the_32_bases(ctx):
+    """The item record carries a 40-bit stream offset, and scan_items, base_at and bg_count_kernel compute with 64-bit
+    offsets: 22M x 200 bp is 4.4e9 bases, so the later half of the items lies above 2^32 -- the smallest size at which a
+    32-bit truncation anywhere on that path shows.  The table, ltot and the 84 counters of the whole must be the sums
+    over the halves [0, n/2) and [n/2, n) (each below 2^32 on its own), in both strand modes and under both emitters;
+    the stand-alone background count must equal the fused one; item_windows must not matter (one item per sequence
+    either way).  If this fails while the checks of the halves among themselves hold, the items above 2^32 are at
+    fault: those below it see the same stream as the first half alone."""
+    n, seed = 22_000_000, 7
+    assert n * L > 2 ** 32 > (n - n // 2) * L
+    combos = [(both, impl) for both in (True, False) for impl in (1, 2)]
+
+    def counts_of(seq0, m, item_windows=0, only=None):
+        ctx.synth(seed, seq0, m, L, W, item_windows)
+        out = {}
+        for both, impl in only or combos:
+            ctx.set_option("count_impl", impl)
+            try:
+                c, lt, bg = ctx.count_bg(both)
+                out[both, impl] = (c.to_host().astype(np.uint64), int(lt.to_host()[0]), bg.to_host())
+            finally:
+                ctx.set_option("count_impl", 0)
+        return out, ctx.bg_count().to_host()
+
+    whole, alone = counts_of(0, n)
+    for key in combos:
+        assert whole[key][1] == n * (L - W + 1), key
+        assert np.array_equal(whole[key][2], alone), key
+    wide, _ = counts_of(0, n, 65535, only=[(True, 2)])
+    assert np.array_equal(wide[True, 2][0], whole[True, 2][0]) and np.array_equal(wide[True, 2][2], whole[True, 2][2])
+    a, _ = counts_of(0, n // 2)
+    b, _ = counts_of(n // 2, n - n // 2)
+    for key in combos:
+        what = "%s, emitter %d" % ("both strands" if key[0] else "plus strand", key[1])
+        assert a[key][1] + b[key][1] == whole[key][1], what
+        got, want = whole[key][0], a[key][0] + b[key][0]
+        bad = np.flatnonzero(got != want)
+        assert not bad.size, "%s: %d bins differ, the first: bin %d, whole %d, halves %d" % (
+            what, bad.size, bad[0], got[bad[0]], want[bad[0]])
+        assert np.array_equal(whole[key][2], a[key][2] + b[key][2]), what
 
 
 def test_direct_and_partitioned_emitters_agree_at_scale(ctx):
