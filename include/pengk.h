@@ -397,6 +397,28 @@ int pengk_score_threshold(const double* h_tail, int32_t lo, int32_t hi, double p
 int pengk_sites_count(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_valid, const int64_t* d_offs,
                       const uint32_t* d_lens, uint64_t n_seq, int n_motifs, const int32_t* h_S, const int32_t* h_len,
                       int both_strands, const int32_t* h_thr, uint64_t* d_counts);
+/* The count pass with the numbers behind the sites' q-values (--sites-qvalue), in one walk over the
+ * sequences.  Motif m owns max(0, h_hi[m] - h_thr[m] + 1) uint64 bins from d_hist + h_hist_offs[m] on: bin s - h_thr[m]
+ * counts the window strands with score exactly s, the sites of pengk_sites_count at the same thresholds.  h_hi[m] is the
+ * sum of the column maxima of S[m] (pengk_score_tail_pvalues' hi_out; anything below it is PENGK_ERR_ARG, since a score
+ * would have no bin).  d_tests[m] (n_motifs uint64) counts the scored window strands of motif m: a window whose bases are
+ * all valid counts once, twice with both_strands.  Both are ADDED to (caller-zeroed): shards and several calls sum
+ * exactly, as in pengk_score_histograms.  d_counts: NULL, or the n_motifs x n_seq array of pengk_sites_count, written
+ * (not added to) with the same values.  d_hist may be NULL when no motif has a bin.  Other arguments as
+ * pengk_sites_count; n_seq = 0 or n_motifs = 0 does nothing. */
+int pengk_sites_histograms(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_valid, const int64_t* d_offs,
+                           const uint32_t* d_lens, uint64_t n_seq, int n_motifs, const int32_t* h_S, const int32_t* h_len,
+                           int both_strands, const int32_t* h_thr, const int32_t* h_hi, const uint64_t* h_hist_offs,
+                           uint64_t* d_hist, uint64_t* d_tests, uint64_t* d_counts);
+/* Pure CPU.  Benjamini-Hochberg q-values of one motif's sites from its histogram (h_hist[k]: the sites with score t + k,
+ * nbins = hi - t + 1 bins, summed over all ranks), the number of tests n_tests (d_tests, summed likewise) and
+ * h_tail_from_thr = tail + (t - lo) of pengk_score_tail_pvalues.  n(k) = sum over k' >= k of h_hist[k'] (uint64, from
+ * the top down); r(k) = (double)n_tests * h_tail_from_thr[k] / (double)n(k) -- one multiplication, then one division --
+ * or +inf when n(k) = 0; h_q[k] = min(1.0, min over k' <= k of r(k')), a running minimum from bin 0 up, so it never
+ * rises with the score.  h_q takes nbins doubles; nbins = 0 does nothing. */
+int pengk_sites_qvalues(const uint64_t* h_hist, uint64_t nbins, uint64_t n_tests, const double* h_tail_from_thr, double* h_q);
+/* Pure CPU.  The smallest score s = t + k, k < nbins, with h_q[k] <= q_max (q_max >= 0), else t + nbins (no site). */
+int pengk_qvalue_threshold(const double* h_q, uint64_t nbins, int32_t t, double q_max, int32_t* t_out);
 /* From d_counts (pengk_sites_count): h_motif_totals[m] = the sites of motif m over all sequences, and the slices
  * [h_bounds[k], h_bounds[k + 1]) of the sequences, k < *n_slices, in order, covering [0, n_seq), with h_records[k] records
  * each.  A slice is as long as its records stay within the option "sites_record_budget" (default 2^24; >= 1, a test

@@ -34,6 +34,7 @@ EXPORTS = [
     "pengk_scan_layout_words", "pengk_scan_layout_build", "pengk_synth_scan_sequences", "pengk_sample_background",
     "pengk_motif_scan", "pengk_score_histograms", "pengk_score_summary",
     "pengk_score_tail_pvalues", "pengk_score_threshold", "pengk_sites_count", "pengk_sites_slices", "pengk_sites_emit",
+    "pengk_sites_histograms", "pengk_sites_qvalues", "pengk_qvalue_threshold",
     "pengk_motif_best_sites", "pengk_centrality_histograms", "pengk_centrality_summary", "pengk_binomial_log10_sf",
     "pengk_site_profiles", "pengk_profile_refine",
 ]
@@ -143,6 +144,9 @@ def lib():
         L.pengk_score_tail_pvalues.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp]
         L.pengk_score_threshold.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, C.POINTER(C.c_int32)]
         L.pengk_sites_count.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, vp, vp, C.c_int, vp, vp]
+        L.pengk_sites_histograms.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
+        L.pengk_sites_qvalues.argtypes = [vp, u64, u64, vp, vp]
+        L.pengk_qvalue_threshold.argtypes = [vp, u64, C.c_int32, C.c_double, C.POINTER(C.c_int32)]
         L.pengk_sites_slices.argtypes = [vp, vp, u64, C.c_int, vp, u64, vp, vp, C.POINTER(u64)]
         L.pengk_sites_emit.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, vp, vp, C.c_int, vp, vp, u64, u64, vp, u64]
         L.pengk_motif_best_sites.argtypes = [vp, vp, vp, vp, vp, u64, u64, C.c_int, vp, vp, C.c_int, vp, vp]
@@ -230,6 +234,25 @@ def score_threshold(tail, lo, p):
     t = C.c_int32()
     _check(lib().pengk_score_threshold(tail.ctypes.data, lo, lo + len(tail) - 1, p, C.byref(t)))
     return t.value
+
+
+def sites_qvalues(hist, n_tests, tail_from_thr):
+    """q[k] of the sites with score t + k from one motif's site histogram (summed over all ranks), its number of scored
+    window strands and tail[t - lo:] of score_tail_pvalues (pengk_sites_qvalues, CPU)"""
+    h = np.ascontiguousarray(hist, np.uint64)
+    tail = np.ascontiguousarray(tail_from_thr, np.float64)
+    assert len(tail) >= len(h)
+    q = np.zeros(len(h), np.float64)
+    _check(lib().pengk_sites_qvalues(h.ctypes.data, len(h), int(n_tests), tail.ctypes.data, q.ctypes.data))
+    return q
+
+
+def qvalue_threshold(q, t, q_max):
+    """the smallest score t + k with q[k] <= q_max, else t + len(q) (pengk_qvalue_threshold, CPU)"""
+    q = np.ascontiguousarray(q, np.float64)
+    out = C.c_int32()
+    _check(lib().pengk_qvalue_threshold(q.ctypes.data, len(q), t, q_max, C.byref(out)))
+    return out.value
 
 
 def centrality_summary(hist_offsets, hist_lengths, max_len, w, n_motifs):
@@ -544,6 +567,30 @@ class Context:
         _check(lib().pengk_sites_count(self.h, _ptr(scan[0]), _ptr(scan[1]), _ptr(scan[2]), _ptr(scan[3]), scan[4], n,
                                        Sp.ctypes.data, ln.ctypes.data, int(both), th.ctypes.data, _ptr(counts)))
         return counts
+
+    def sites_histograms(self, scan, S, lens, both, thr, hi, counts=None, hist=None, tests=None, offs=None):
+        """(hists, tests): hists[m] (uint64, max(0, hi[m] - thr[m] + 1) bins) the sites of motif m by score - thr[m], tests[m]
+        its scored window strands (pengk_sites_histograms; downloaded).  counts: a device n_motifs x n_seq uint64 array
+        to fill as sites_count does.  hist / tests: device uint64 arrays to ADD to instead of fresh zeroed ones (motif m's
+        bins from hist[offs[m]] on, default back to back); what is returned is then their content after the call."""
+        n = len(lens)
+        Sp, ln = _pad_motifs(S, lens)
+        th = np.ascontiguousarray(thr, np.int32)
+        hi = np.ascontiguousarray(hi, np.int32)
+        nb = np.maximum(hi.astype(np.int64) - th.astype(np.int64) + 1, 0)
+        if offs is None:
+            offs = np.concatenate([[0], np.cumsum(nb)])[:max(n, 1)]
+        offs = np.ascontiguousarray(offs, np.uint64)
+        if hist is None:
+            hist = self.to_device(np.zeros(max(int(nb.sum()), 1), np.uint64))
+        if tests is None:
+            tests = self.to_device(np.zeros(max(n, 1), np.uint64))
+        _check(lib().pengk_sites_histograms(self.h, _ptr(scan[0]), _ptr(scan[1]), _ptr(scan[2]), _ptr(scan[3]), scan[4], n,
+                                            Sp.ctypes.data, ln.ctypes.data, int(both), th.ctypes.data, hi.ctypes.data,
+                                            offs.ctypes.data, _ptr(hist), _ptr(tests),
+                                            _ptr(counts) if counts is not None else None))
+        h = hist.to_host()
+        return [h[int(offs[m]):int(offs[m]) + int(nb[m])].copy() for m in range(n)], tests.to_host()[:n]
 
     def sites_slices(self, counts, n_seq, n_motifs):
         """(bounds, records, motif_totals) of pengk_sites_slices"""

@@ -683,6 +683,136 @@ __global__ __launch_bounds__(PROF_THREADS) void site_profile_kernel(const uint64
     if (bins[k]) atomicAdd(&out[k], (unsigned long long)bins[k]);
 }
 
+// ---- site histograms (pengk_sites_histograms: the ranks behind --sites-qvalue) -------------------------
+constexpr int QH_PRIV_BINS = 2560;          // workgroup-private 32-bit bins (10 KiB), shared evenly by the group's motifs
+constexpr uint32_t QH_LONG_SEQ = 1u << 16;  // a longer sequence adds to the global bins only
+constexpr int QH_FLUSH_TRIPS = 64;          // trips of the workgroup's sequence loop between two flushes of the private bins
+
+// Per motif of the group: the global bins (bin 0 = the threshold), the lowest score with a private bin, the scored
+// window strands of the workgroup.
+struct HistRec {
+  unsigned long long* H;
+  unsigned long long tests;
+  int32_t thr, top;
+};
+
+// A fourth visitor: every site adds 1 to its motif's bin score - t, every valid window counts as one or two scored
+// strands, and the per-(motif, sequence) site count is CountVisit's.  The top `per` scores of each motif of the group
+// (where a motif that sits in every sequence sends its sites) have a workgroup-private 32-bit bin in LDS; a lower score
+// adds to the global uint64 bin directly.
+// No private bin can wrap: a thread adds to it only for a sequence of at most QH_LONG_SEQ = 2^16 bases, so at most 2^17
+// times per trip of the workgroup's loop (one sequence per thread and trip, two strands per window); 256 threads and
+// QH_FLUSH_TRIPS = 64 trips between two flushes bound a bin by 2^8 * 2^17 * 2^6 = 2^31 < 2^32.  A longer sequence (up to
+// 2^33 window strands) gets top = INT32_MAX, which no score reaches: all its sites go to the global bins.
+template <bool BOTH>
+struct HistVisit {
+  const MotifRec* mrec;
+  HistRec* hrec;
+  uint32_t* priv;
+  unsigned long long* counts;  // NULL: not stored
+  uint64_t n_seq, i;
+  int per;
+  bool short_seq;
+  int32_t t[SCAN_PASS], top[SCAN_PASS], pb[SCAN_PASS], r[SCAN_PASS];
+  uint32_t nw[SCAN_PASS];
+  unsigned long long c[SCAN_PASS];
+  __device__ __forceinline__ void begin(int q, int rr) {
+    r[q] = rr;
+    t[q] = hrec[rr].thr;
+    top[q] = short_seq ? hrec[rr].top : INT32_MAX;
+    pb[q] = rr * per - hrec[rr].top;  // private bin of score s: priv[pb + s], in [rr * per, (rr + 1) * per) for top <= s <= hi
+    nw[q] = 0;
+    c[q] = 0;
+  }
+  __device__ __forceinline__ void bump(int q, int32_t sc) {
+    if (sc >= top[q]) atomicAdd(&priv[pb[q] + sc], 1u);
+    else atomicAdd(&hrec[r[q]].H[(int64_t)sc - t[q]], 1ull);
+    ++c[q];
+  }
+  __device__ __forceinline__ void window(int q, uint32_t, int32_t sf, int32_t sr) {
+    ++nw[q];
+    if (sf >= t[q]) bump(q, sf);
+    if (BOTH && sr >= t[q]) bump(q, sr);
+  }
+  __device__ __forceinline__ void end(int q, int rr) {
+    if (nw[q]) atomicAdd(&hrec[rr].tests, (unsigned long long)nw[q] * (BOTH ? 2u : 1u));
+    if (counts) counts[(uint64_t)mrec[rr].m * n_seq + i] = c[q];
+  }
+};
+
+// a kernel of its own: the count pass of --sites keeps its code when q-values are not asked for
+template <bool BOTH>
+__global__ __launch_bounds__(SCAN_THREADS) void motif_sites_hist_kernel(const uint64_t* __restrict__ words,
+                                                                        const uint32_t* __restrict__ valid,
+                                                                        const int64_t* __restrict__ offs,
+                                                                        const uint32_t* __restrict__ lens, uint64_t n_seq,
+                                                                        const int32_t* __restrict__ tables,
+                                                                        const MotifRec* __restrict__ recs,
+                                                                        const GroupRec* __restrict__ groups,
+                                                                        const int32_t* __restrict__ thr,
+                                                                        const int32_t* __restrict__ hi,
+                                                                        const uint64_t* __restrict__ hoffs,
+                                                                        unsigned long long* __restrict__ hist,
+                                                                        unsigned long long* __restrict__ tests,
+                                                                        unsigned long long* __restrict__ counts) {
+  __shared__ int32_t tab[SCAN_TABLES * 256];
+  __shared__ MotifRec mrec[SCAN_MAX_MOTIFS];
+  __shared__ HistRec hrec[SCAN_MAX_MOTIFS];
+  __shared__ uint32_t priv[QH_PRIV_BINS];
+  const GroupRec g = groups[blockIdx.y];
+  const int nrec = g.m1 - g.m0;
+  const int per = QH_PRIV_BINS / nrec;  // (1 <= nrec <= SCAN_MAX_MOTIFS: at least 64 bins each)
+  for (int t = threadIdx.x; t < g.n_ints; t += SCAN_THREADS) tab[t] = tables[g.table0 + t];
+  for (int t = threadIdx.x; t < nrec; t += SCAN_THREADS) {
+    const MotifRec mr = recs[g.m0 + t];
+    mrec[t] = mr;
+    // the private bins: scores (hi - per, hi], none below the threshold (hi >= every score: the host checked it)
+    const int64_t tp = (int64_t)hi[mr.m] - per + 1;
+    HistRec h;
+    h.H = hist + hoffs[mr.m];
+    h.tests = 0;
+    h.thr = thr[mr.m];
+    h.top = tp > (int64_t)h.thr ? (int32_t)tp : h.thr;
+    hrec[t] = h;
+  }
+  for (int t = threadIdx.x; t < QH_PRIV_BINS; t += SCAN_THREADS) priv[t] = 0;
+  __syncthreads();
+  // private bin k of record k / per holds score top + k % per: bin top - thr + k % per of the motif (a bin above hi - thr
+  // is never added to and stays 0)
+  auto flush = [&]() {
+    for (int k = threadIdx.x; k < nrec * per; k += SCAN_THREADS) {
+      const uint32_t n = priv[k];
+      if (n) {
+        const int rr = k / per;
+        atomicAdd(&hrec[rr].H[(int64_t)hrec[rr].top - hrec[rr].thr + (k - rr * per)], (unsigned long long)n);
+        priv[k] = 0;
+      }
+    }
+  };
+  // (every thread of the workgroup makes the same trips: the flush inside the loop is reached by all of them)
+  int trips = 0;
+  for (uint64_t ib = blockIdx.x * (uint64_t)SCAN_THREADS; ib < n_seq; ib += (uint64_t)gridDim.x * SCAN_THREADS) {
+    const uint64_t i = ib + threadIdx.x;
+    if (i < n_seq) {
+      const uint32_t L = lens[i];
+      const uint64_t w0 = (uint64_t)offs[i] >> 5;
+      HistVisit<BOTH> v{mrec, hrec, priv, counts, n_seq, i, per, L <= QH_LONG_SEQ, {}, {}, {}, {}, {}, {}};
+      walk_sequence<BOTH>(words + w0, valid ? valid + w0 : nullptr, L, tab, mrec, nrec, v);
+    }
+    if (++trips == QH_FLUSH_TRIPS) {
+      __syncthreads();
+      flush();
+      __syncthreads();
+      trips = 0;
+    }
+  }
+  __syncthreads();
+  flush();
+  // the scored window strands: one global atomic per motif and workgroup
+  for (int t = threadIdx.x; t < nrec; t += SCAN_THREADS)
+    if (hrec[t].tests) atomicAdd(&tests[mrec[t].m], hrec[t].tests);
+}
+
 int grid_for(pengk_ctx* ctx, uint64_t work, uint32_t per_block, uint32_t per_cu) {
   const uint64_t need = (work + per_block - 1) / per_block;
   const uint64_t cap = (uint64_t)ctx->num_cu * per_cu;
@@ -1076,6 +1206,85 @@ int pengk_sites_count(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d
     hipLaunchKernelGGL((motif_sites_kernel<false, false>), grid, dim3(SCAN_THREADS), 0, ctx->stream, d_words, d_valid, d_offs, d_lens,
                        (uint64_t)0, n_seq, n_seq, st.tables, st.recs, st.groups, st.thr, c, nullptr, nullptr, (uint64_t)0);
   PENGK_HIP(hipGetLastError());
+  return PENGK_OK;
+}
+
+int pengk_sites_histograms(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_valid, const int64_t* d_offs,
+                           const uint32_t* d_lens, uint64_t n_seq, int n_motifs, const int32_t* h_S, const int32_t* h_len,
+                           int both_strands, const int32_t* h_thr, const int32_t* h_hi, const uint64_t* h_hist_offs,
+                           uint64_t* d_hist, uint64_t* d_tests, uint64_t* d_counts) {
+  if (!ctx || n_motifs < 0 || (n_motifs && (!h_S || !h_len || !h_thr || !h_hi || !h_hist_offs || !d_tests)) ||
+      (n_seq && n_motifs && (!d_words || !d_offs || !d_lens)))
+    return fail(PENGK_ERR_ARG, "pengk_sites_histograms: bad argument");
+  int rc = check_motifs("pengk_sites_histograms", n_motifs, h_S, h_len);
+  if (rc) return rc;
+  // every score must have its bin: h_hi[m] at or above the sum of the column maxima, and bins to add to
+  for (int m = 0; m < n_motifs; ++m) {
+    int32_t mx = 0;
+    for (int j = 0; j < h_len[m]; ++j) {
+      const int32_t* c = h_S + ((size_t)m * PENGK_MAX_MOTIF_LEN + j) * 4;
+      mx += std::max(std::max(c[0], c[1]), std::max(c[2], c[3]));
+    }
+    if (h_hi[m] < mx) return fail(PENGK_ERR_ARG, "pengk_sites_histograms: motif %d: hi %d below its best score %d", m, h_hi[m], mx);
+    if (h_hi[m] >= h_thr[m] && !d_hist) return fail(PENGK_ERR_ARG, "pengk_sites_histograms: bad argument");
+  }
+  SCORE_ENTER(ctx);
+  if (n_seq == 0 || n_motifs == 0) return PENGK_OK;
+  const size_t hb = ((size_t)n_motifs * sizeof(int32_t) + 7) & ~(size_t)7;
+  std::vector<char> staged(hb + (size_t)n_motifs * sizeof(uint64_t));
+  memcpy(staged.data(), h_hi, (size_t)n_motifs * sizeof(int32_t));
+  memcpy(staged.data() + hb, h_hist_offs, (size_t)n_motifs * sizeof(uint64_t));
+  rc = ensure_scratch(ctx, &ctx->d_misc, &ctx->misc_bytes, staged.size());
+  if (rc) return rc;
+  StagedMotifs st;
+  rc = stage_motifs(ctx, n_motifs, h_S, h_len, both_strands ? 2 : 1, h_thr, &st);  // (synchronises with the stream)
+  if (rc) return rc;
+  PENGK_HIP(hipMemcpy(ctx->d_misc, staged.data(), staged.size(), hipMemcpyHostToDevice));
+  const int32_t* d_hi = (const int32_t*)ctx->d_misc;
+  const uint64_t* d_ho = (const uint64_t*)((char*)ctx->d_misc + hb);
+  const dim3 grid(grid_for(ctx, n_seq, SCAN_THREADS, 8), (unsigned)st.n_groups);
+  unsigned long long* h = (unsigned long long*)d_hist;
+  unsigned long long* t = (unsigned long long*)d_tests;
+  unsigned long long* c = (unsigned long long*)d_counts;
+  if (both_strands)
+    hipLaunchKernelGGL(motif_sites_hist_kernel<true>, grid, dim3(SCAN_THREADS), 0, ctx->stream, d_words, d_valid, d_offs, d_lens,
+                       n_seq, st.tables, st.recs, st.groups, st.thr, d_hi, d_ho, h, t, c);
+  else
+    hipLaunchKernelGGL(motif_sites_hist_kernel<false>, grid, dim3(SCAN_THREADS), 0, ctx->stream, d_words, d_valid, d_offs, d_lens,
+                       n_seq, st.tables, st.recs, st.groups, st.thr, d_hi, d_ho, h, t, c);
+  PENGK_HIP(hipGetLastError());
+  return PENGK_OK;
+}
+
+int pengk_sites_qvalues(const uint64_t* h_hist, uint64_t nbins, uint64_t n_tests, const double* h_tail_from_thr, double* h_q) {
+  if (nbins && (!h_hist || !h_tail_from_thr || !h_q)) return fail(PENGK_ERR_ARG, "pengk_sites_qvalues: bad argument");
+  // r(s) = N * tail / n(s), the ranks n(s) summed from the highest score down
+  const double N = (double)n_tests;
+  uint64_t n = 0;
+  for (uint64_t k = nbins; k-- > 0;) {
+    n += h_hist[k];
+    if (n > 0) {
+      const double x = N * h_tail_from_thr[k];
+      h_q[k] = x / (double)n;
+    } else {
+      h_q[k] = INFINITY;
+    }
+  }
+  // q(s) = min(1, min over s' <= s of r(s')), a running minimum from the threshold up
+  double mn = INFINITY;
+  for (uint64_t k = 0; k < nbins; ++k) {
+    if (h_q[k] < mn) mn = h_q[k];
+    h_q[k] = mn < 1.0 ? mn : 1.0;
+  }
+  return PENGK_OK;
+}
+
+int pengk_qvalue_threshold(const double* h_q, uint64_t nbins, int32_t t, double q_max, int32_t* t_out) {
+  if (!t_out || (nbins && !h_q) || !(q_max >= 0.0) || (int64_t)t + (int64_t)nbins > (int64_t)INT32_MAX || nbins > (1ull << 32))
+    return fail(PENGK_ERR_ARG, "pengk_qvalue_threshold: bad argument");
+  uint64_t k = 0;
+  while (k < nbins && !(h_q[k] <= q_max)) ++k;
+  *t_out = (int32_t)((int64_t)t + (int64_t)k);
   return PENGK_OK;
 }
 

@@ -46,6 +46,8 @@ bool Global::scoreMotifs = false;
 unsigned long long Global::scoreSeed = 1;
 char* Global::sitesFilename = nullptr;
 double Global::sitesPvalue = 1e-4;
+bool Global::sitesQvalue = false;
+double Global::sitesQvalueMax = 0.0;
 char* Global::centralityFilename = nullptr;
 double Global::centralityPvalue = 1e-4;
 char* Global::refineFilename = nullptr;
@@ -213,6 +215,18 @@ void Global::readArguments(int nargs, char* args[]) {
         log_line("ERROR", "--sites-pvalue must be a number in (0, 1]");
         exit(4);
       }
+    } else if (!strcmp(a, "--sites-qvalue")) {
+      sitesQvalue = true;
+    } else if (!strcmp(a, "--sites-qvalue-max")) {
+      const char* v = need(i, nargs, args, printHelp);
+      char* end = nullptr;
+      sitesQvalueMax = std::strtod(v, &end);
+      if (end == v || *end || !(sitesQvalueMax > 0.0 && sitesQvalueMax <= 1.0)) {
+        printHelp();
+        log_line("ERROR", "--sites-qvalue-max must be a number in (0, 1]");
+        exit(4);
+      }
+      sitesQvalue = true;
     } else if (!strcmp(a, "--centrality")) {
       centralityFilename = (char*)need(i, nargs, args, printHelp);
     } else if (!strcmp(a, "--centrality-pvalue")) {
@@ -300,6 +314,10 @@ void Global::printHelp() {
   printf("  --sites FILE                   write every occurrence of the motifs (TSV: sequence, position, strand,\n");
   printf("                                 score, p-value) at p-value --sites-pvalue or below\n");
   printf("  --sites-pvalue FLOAT           p-value threshold of --sites, in (0, 1] (default 1e-4)\n");
+  printf("  --sites-qvalue                 add a q_value column to --sites: Benjamini-Hochberg over each motif's sites,\n");
+  printf("                                 with all its scored window strands as the number of tests\n");
+  printf("  --sites-qvalue-max FLOAT       write only the sites with a q-value at or below this, in (0, 1] (implies\n");
+  printf("                                 --sites-qvalue)\n");
   printf("  --centrality FILE              test every motif for enrichment at the sequence centres (TSV: best site\n");
   printf("                                 per sequence at p-value --centrality-pvalue or below, binomial test)\n");
   printf("  --centrality-pvalue FLOAT      p-value threshold of a best site, in (0, 1] (default 1e-4)\n");

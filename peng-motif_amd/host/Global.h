@@ -61,6 +61,8 @@ class Global {
   static unsigned long long scoreSeed;       // --score-seed
   static char* sitesFilename;                // --sites (new: every motif occurrence with its p-value)
   static double sitesPvalue;                 // --sites-pvalue
+  static bool sitesQvalue;                   // --sites-qvalue (new: a q-value column in the sites file)
+  static double sitesQvalueMax;              // --sites-qvalue-max (0: every site at --sites-pvalue)
   static char* centralityFilename;           // --centrality (new: central enrichment of the motifs)
   static double centralityPvalue;            // --centrality-pvalue
   static char* refineFilename;               // --refine (new: the motifs re-estimated from their sites)

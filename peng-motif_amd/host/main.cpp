@@ -136,7 +136,7 @@ int main(int nargs, char** args) {
     std::sort(meme_order.begin(), meme_order.end(), sort_IUPAC_patterns);
   if (Global::sitesFilename) {
     write_motif_sites(meme_order, *Global::inputSequenceSet, *scan, *bgModel, Global::strand == Strand::BOTH_STRANDS,
-                      Global::sitesPvalue, Global::sitesFilename);
+                      Global::sitesPvalue, Global::sitesQvalue, Global::sitesQvalueMax, Global::sitesFilename);
     clock.lap("sites");
   }
   if (Global::centralityFilename) {

@@ -3,6 +3,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <iostream>
 #include <thread>
@@ -23,11 +24,12 @@ struct MotifInfo {
   int w = 0;
   int32_t lo = 0, hi = 0, t = 0;
   std::vector<double> tail;  // P(score >= s) at tail[s - lo]
+  std::vector<double> q;     // (--sites-qvalue) the q-value of a site with score s at q[s - t]
 };
 }  // namespace
 
 void write_motif_sites(const std::vector<IUPACPattern*>& pats, SequenceSet& set, const ScanInput& in, BackgroundModel& bg,
-                       bool both_strands, double pvalue, const std::string& path) {
+                       bool both_strands, double pvalue, bool qvalues, double qvalue_max, const std::string& path) {
   using pengk_host::check;
   using pengk_host::DeviceBuffer;
   pengk_host::Lap lap("  sites: ");
@@ -50,6 +52,24 @@ void write_motif_sites(const std::vector<IUPACPattern*>& pats, SequenceSet& set,
     check(pengk_score_threshold(x.tail.data(), x.lo, x.hi, pvalue, &x.t), "pengk_score_threshold");
     thr[m] = x.t;
   }
+  // PENGK_SITES_SCORES=FILE (diagnostic): the integer log-odds matrices as scanned -- per motif a line "index width lo hi
+  // threshold", then its rows.  The PWMs of the MEME / JSON files are rounded, and written after the writers' pseudo
+  // count: they do not give these integers back.
+  if (const char* dump = std::getenv("PENGK_SITES_SCORES")) {
+    if (pengk_host::rank() == 0) {
+      FILE* f = fopen(dump, "wb");
+      if (f) {
+        for (int m = 0; m < n_motifs; ++m) {
+          fprintf(f, "%d %d %d %d %d\n", m + 1, mi[m].w, mi[m].lo, mi[m].hi, mi[m].t);
+          for (int j = 0; j < mi[m].w; ++j) {
+            const int32_t* r = &S[((size_t)m * PENGK_MAX_MOTIF_LEN + j) * 4];
+            fprintf(f, "%d %d %d %d\n", r[0], r[1], r[2], r[3]);
+          }
+        }
+        fclose(f);
+      }
+    }
+  }
   lap("thresholds");
 
   // where local record k lives: the chunk that holds it
@@ -65,11 +85,58 @@ void write_motif_sites(const std::vector<IUPACPattern*>& pats, SequenceSet& set,
   std::vector<std::string> out(n_motifs);
   pengk_ctx* ctx = pengk_host::context();
   const int both = both_strands ? 1 : 0;
-  if (n_motifs && n_local) {
-    DeviceBuffer<uint64_t> d_counts((size_t)n_motifs * n_local);
-    check(pengk_sites_count(ctx, in.d_words.get(), in.d_valid.get(), in.d_offs.get(), in.d_lens.get(), n_local, n_motifs, S.data(),
-                            len.data(), both, thr.data(), d_counts.get()),
-          "pengk_sites_count");
+  const bool scan = n_motifs && n_local;
+  DeviceBuffer<uint64_t> d_counts;
+  if (scan) d_counts.resize((size_t)n_motifs * n_local);
+  if (!qvalues) {
+    if (scan)
+      check(pengk_sites_count(ctx, in.d_words.get(), in.d_valid.get(), in.d_offs.get(), in.d_lens.get(), n_local, n_motifs,
+                              S.data(), len.data(), both, thr.data(), d_counts.get()),
+            "pengk_sites_count");
+  } else if (n_motifs) {
+    // the count pass with the histograms of the site scores and the scored window strands; their sums over the ranks
+    // (integers) give every rank the same q-values
+    std::vector<int32_t> hi(n_motifs);
+    std::vector<uint64_t> hoffs(n_motifs);
+    size_t nh = 0;
+    for (int m = 0; m < n_motifs; ++m) {
+      hi[m] = mi[m].hi;
+      hoffs[m] = nh;
+      nh += (size_t)std::max<int64_t>(0, (int64_t)mi[m].hi - mi[m].t + 1);
+    }
+    std::vector<long long> hist(nh + n_motifs, 0);  // the bins, then N_m
+    if (scan) {
+      DeviceBuffer<uint64_t> d_hist(nh + n_motifs);
+      check(pengk_memset(ctx, d_hist.get(), 0, (nh + n_motifs) * sizeof(uint64_t)), "pengk_memset");
+      check(pengk_sites_histograms(ctx, in.d_words.get(), in.d_valid.get(), in.d_offs.get(), in.d_lens.get(), n_local, n_motifs,
+                                   S.data(), len.data(), both, thr.data(), hi.data(), hoffs.data(), d_hist.get(),
+                                   d_hist.get() + nh, d_counts.get()),
+            "pengk_sites_histograms");
+      d_hist.download((uint64_t*)hist.data(), nh + n_motifs);
+    }
+    lap("count + histograms");
+    SequenceSet::allreduceSum(hist.data(), hist.size());  // (integers: the ranks' sum is exact)
+    bool raised = false;
+    for (int m = 0; m < n_motifs; ++m) {
+      MotifInfo& x = mi[m];
+      const uint64_t nb = (uint64_t)std::max<int64_t>(0, (int64_t)x.hi - x.t + 1);
+      x.q.resize(nb);
+      check(pengk_sites_qvalues((const uint64_t*)hist.data() + hoffs[m], nb, (uint64_t)hist[nh + m],
+                                nb ? x.tail.data() + (x.t - x.lo) : nullptr, x.q.data()),
+            "pengk_sites_qvalues");
+      if (qvalue_max > 0.0) {
+        check(pengk_qvalue_threshold(x.q.data(), nb, x.t, qvalue_max, &thr[m]), "pengk_qvalue_threshold");
+        raised = true;
+      }
+    }
+    // --sites-qvalue-max: the sites at the raised thresholds (the q-values stay those of the set at `pvalue`)
+    if (raised && scan)
+      check(pengk_sites_count(ctx, in.d_words.get(), in.d_valid.get(), in.d_offs.get(), in.d_lens.get(), n_local, n_motifs,
+                              S.data(), len.data(), both, thr.data(), d_counts.get()),
+            "pengk_sites_count");
+    lap("q-values");
+  }
+  if (scan) {
     std::vector<uint64_t> mtot(n_motifs), bounds(65), recs(64);
     uint64_t ns = 0;
     for (;;) {
@@ -132,6 +199,10 @@ void write_motif_sites(const std::vector<IUPACPattern*>& pats, SequenceSet& set,
               put_score(o, st.score);
               snprintf(b, sizeof b, "\t%.3g\t", x.tail[(size_t)(st.score - x.lo)]);
               o += b;
+              if (qvalues) {
+                snprintf(b, sizeof b, "%.3g\t", x.q[(size_t)(st.score - x.t)]);
+                o += b;
+              }
               const uint8_t* c = codes_of(k) + st.pos;
               for (int j = 0; j < x.w; ++j) o += minus ? "TGCA"[c[x.w - 1 - j] - 1] : "ACGT"[c[j] - 1];
               o += '\n';
@@ -141,6 +212,7 @@ void write_motif_sites(const std::vector<IUPACPattern*>& pats, SequenceSet& set,
       for (auto& x : th) x.join();
       for (Piece& pc : pieces) out[pc.m] += pc.s;
     }
+    d_counts.release();
     lap("emit + format");
   }
 
@@ -181,7 +253,8 @@ void write_motif_sites(const std::vector<IUPACPattern*>& pats, SequenceSet& set,
     std::cerr << "Unable to open output file (" << path << ")!" << std::endl;
     exit(1);
   }
-  const char* head = "#motif_index\tmotif_id\tsequence_name\tstart\tstop\tstrand\tscore\tp_value\tmatched_sequence\n";
+  const char* head = qvalues ? "#motif_index\tmotif_id\tsequence_name\tstart\tstop\tstrand\tscore\tp_value\tq_value\tmatched_sequence\n"
+                             : "#motif_index\tmotif_id\tsequence_name\tstart\tstop\tstrand\tscore\tp_value\tmatched_sequence\n";
   bool ok = fwrite(head, 1, strlen(head), f) == strlen(head);
   std::vector<uint64_t> pos(R, 0);
   for (int m = 0; m < n_motifs; ++m) {
