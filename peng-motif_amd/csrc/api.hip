@@ -245,8 +245,8 @@ int pengk_get_info(pengk_ctx* ctx, const char* name, int64_t* value) {
   PENGK_ENTER(ctx);
   if (strcmp(name, "deferred_items") == 0) {  // scan items the last pengk_count handed to the exact fallback
     uint32_t n = 0;
-    if (ctx->d_defer) {
-      PENGK_HIP(hipMemcpyAsync(&n, ctx->d_defer, sizeof n, hipMemcpyDeviceToHost, ctx->stream));
+    if (ctx->d_defer_count) {
+      PENGK_HIP(hipMemcpyAsync(&n, ctx->d_defer_count, sizeof n, hipMemcpyDeviceToHost, ctx->stream));
       PENGK_HIP(hipStreamSynchronize(ctx->stream));
     }
     *value = n;

@@ -171,7 +171,8 @@ struct Suppress {
 template <int W, bool BOTH, bool BG, class Emit>
 __device__ __forceinline__ void scan_items(const uint32_t* __restrict__ words32, const uint64_t* __restrict__ items,
                                            uint32_t n_items, unsigned long long* __restrict__ ltot,
-                                           uint32_t* __restrict__ defer, Emit& emit) {
+                                           uint32_t* __restrict__ defer_count, uint32_t* __restrict__ defer_list,
+                                           Emit& emit) {
   using G = Geo<W>;
   const BgCount<W, BG> bgc{threadIdx.x >> 6};
   const uint32_t lane_global = blockIdx.x * blockDim.x + threadIdx.x;
@@ -246,8 +247,8 @@ __device__ __forceinline__ void scan_items(const uint32_t* __restrict__ words32,
         }
       }
       if (cont && dirty) {  // cannot certify the ring: hand the item to the exact fallback
-        const uint32_t slot = atomicAdd(&defer[0], 1u);
-        defer[1 + slot] = it;
+        const uint32_t slot = atomicAdd(defer_count, 1u);
+        defer_list[slot] = it;
         nw = 0;
       }
     } else {
@@ -296,44 +297,58 @@ __device__ __forceinline__ void scan_items(const uint32_t* __restrict__ words32,
         view[j] = funnel(chunk, pchunk, 2u * (uint32_t)(j * G::PER + 17 - W));
         rview[j] = BOTH ? funnel(rprev, rchunk, 2u * (uint32_t)(j * G::PER + 17 - W)) : 0u;
       }
-      // Two bodies.  FULL (wave-uniform: every lane owns all 16 windows of this chunk -- all chunks but the last of
+      // Three bodies.  FULL (wave-uniform: every lane owns all 16 windows of this chunk -- all chunks but the last of
       // equally long items): no per-window range tests, suppressed windows travel as INVALID_ID keys, and the fused
-      // K1b counts one 4-mer per two bases.  Otherwise the per-window predicates decide.
-      auto body = [&](auto full_tag) {
-        constexpr bool FULL = decltype(full_tag)::value;
+      // K1b counts one 4-mer per two bases.  TAIL (wave-uniform too: the last chunk of equally long items, `tail`
+      // = 1 .. 15 windows in every lane): the full body's code for the windows u < tail, left by a scalar branch;
+      // an odd tail's last window has no partner for a 4-mer and counts its 3-mer.  Otherwise (items of mixed
+      // lengths, dead lanes, deferred items) the per-window predicates decide.
+      auto body = [&](auto mode_tag, uint32_t tail) {  // (one instantiation per call site: each is inlined)
+        constexpr bool TAIL = decltype(mode_tag)::value == 2;
+        constexpr bool FULL = decltype(mode_tag)::value != 0;
 #pragma unroll
         for (int u = 0; u < 16; ++u) {
-          uint32_t id_u, rc_u = 0;
-          if (u >= W - 1) {  // the window lies inside this chunk
-            id_u = __builtin_amdgcn_ubfe(chunk, 2u * (uint32_t)(u - (W - 1)), 2u * W);
-            if (BOTH) rc_u = __builtin_amdgcn_ubfe(rchunk, 2u * (uint32_t)(15 - u), 2u * W);
-          } else {
-            const int j = u / G::PER, k = W - 2 - u, jr = k / G::PER;
-            id_u = __builtin_amdgcn_ubfe(view[j], 2u * (uint32_t)(u - j * G::PER), 2u * W);
-            if (BOTH) rc_u = __builtin_amdgcn_ubfe(rview[jr], 2u * (uint32_t)(k - jr * G::PER), 2u * W);
-          }
-          const uint32_t can = BOTH ? min(id_u, rc_u) : id_u;
-#ifdef PENGK_ABLATE_NOSUPPRESS  // timing experiment only (WRONG counts on repeats): what a free repeat pre-filter could gain at most
-          const uint32_t key = can;
-#else
-          const uint32_t key = Suppress<W>::apply(can, ring, u);  // INVALID_ID iff one of the last W-1 counted ids
-#endif
-          ring[u] = key;
-          if (FULL) {
-            if (BG && (u & 1)) {  // 4-mer ending on base u: bases u-3 .. u
-              const uint32_t v4 = u >= 3 ? __builtin_amdgcn_ubfe(chunk, 2u * (uint32_t)(u - 3), 8u)
-                                         : funnel(chunk, pchunk, 2u * (uint32_t)(13 + u)) & 0xFFu;
-              bgc.kmer4(v4);
+          if (!TAIL || (uint32_t)u < tail) {  // (a scalar branch: tail is wave-uniform)
+            uint32_t id_u, rc_u = 0;
+            if (u >= W - 1) {  // the window lies inside this chunk
+              id_u = __builtin_amdgcn_ubfe(chunk, 2u * (uint32_t)(u - (W - 1)), 2u * W);
+              if (BOTH) rc_u = __builtin_amdgcn_ubfe(rchunk, 2u * (uint32_t)(15 - u), 2u * W);
+            } else {
+              const int j = u / G::PER, k = W - 2 - u, jr = k / G::PER;
+              id_u = __builtin_amdgcn_ubfe(view[j], 2u * (uint32_t)(u - j * G::PER), 2u * W);
+              if (BOTH) rc_u = __builtin_amdgcn_ubfe(rview[jr], 2u * (uint32_t)(k - jr * G::PER), 2u * W);
             }
-            emit.full(key);
-          } else {
-            bgc.kmer3(id_u, t0 + (uint32_t)u < nw_all);
-            emit.masked(key, key != INVALID_ID && t0 + (uint32_t)u < nw);
+            const uint32_t can = BOTH ? min(id_u, rc_u) : id_u;
+#ifdef PENGK_ABLATE_NOSUPPRESS  // timing experiment only (WRONG counts on repeats): what a free repeat pre-filter could gain at most
+            const uint32_t key = can;
+#else
+            const uint32_t key = Suppress<W>::apply(can, ring, u);  // INVALID_ID iff one of the last W-1 counted ids
+#endif
+            ring[u] = key;
+            if (FULL) {
+              if (BG && (u & 1)) {  // 4-mer ending on base u: bases u-3 .. u
+                const uint32_t v4 = u >= 3 ? __builtin_amdgcn_ubfe(chunk, 2u * (uint32_t)(u - 3), 8u)
+                                           : funnel(chunk, pchunk, 2u * (uint32_t)(13 + u)) & 0xFFu;
+                bgc.kmer4(v4);
+              } else if (TAIL && BG && (uint32_t)u + 1u == tail) {
+                bgc.kmer3(id_u, true);
+              }
+              emit.full(key);
+            } else {
+              bgc.kmer3(id_u, t0 + (uint32_t)u < nw_all);
+              emit.masked(key, key != INVALID_ID && t0 + (uint32_t)u < nw);
+            }
           }
         }
       };
-      if (__all((t0 + 16u <= nw && nw == nw_all) ? 1 : 0)) body(std::true_type{});
-      else body(std::false_type{});
+      if (__all((t0 + 16u <= nw && nw == nw_all) ? 1 : 0)) {
+        body(std::integral_constant<int, 1>{}, 16u);
+      } else {
+        // every lane has the first lane's window count and none was deferred (a dead lane has nw = 0 < t0 + 1)
+        const uint32_t nw0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)nw);
+        if (__all((nw == nw0 && nw == nw_all) ? 1 : 0)) body(std::integral_constant<int, 2>{}, nw0 - t0);
+        else body(std::integral_constant<int, 0>{}, 0u);
+      }
       pchunk = chunk;
       rprev = rchunk;
     }
@@ -367,7 +382,7 @@ __global__ __launch_bounds__(256) void count_kernel(const uint32_t* __restrict__
   bg_begin<BG>();
   if (BG) __syncthreads();
   DirectEmit e{hist};
-  scan_items<W, BOTH, BG>(words32, items, n_items, ltot, defer, e);
+  scan_items<W, BOTH, BG>(words32, items, n_items, ltot, defer, defer + 1, e);
   bg_end<BG>(bg_partials);
 }
 
@@ -384,10 +399,11 @@ __global__ __launch_bounds__(256) void count_kernel(const uint32_t* __restrict__
 //   pass B  count_hist_kernel: a workgroup owns part of one bucket, keeps the bucket's 2^15 bins in
 //           128 KiB of LDS, streams the slices (16 B per lane) and counts with LDS atomics; the
 //           block histogram is added to a bucket-major table with coalesced atomics.
-//   pass C  count_gather_kernel: table[join(bucket, payload)] += bucket-major table.
+//   pass C  count_gather_kernel: table[join(bucket, payload)] = bucket-major table (W = 12, 14: += ).
 //
 // Skewed inputs cannot break it: a slice that runs full makes further groups of that (wave, bucket)
-// fall back to direct atomics on the final table (graceful degradation to variant 1).
+// fall back to direct atomics (graceful degradation to variant 1) -- on the bucket-major table at W = 8, 10,
+// where one launch sequence (launch_partition_w) clears once and runs three kernels, on the final table above.
 // ---------------------------------------------------------------------------------------------
 constexpr int RING_CAP = 128;           // u16 entries per (wave, bucket) ring: a group of 64 plus 64 in flight
 constexpr int GROUP = RING_CAP / 2;        // entries written per flush (one 128-byte line at RING_CAP = 128)
@@ -661,22 +677,33 @@ struct ScatterEmit {
 #define PENGK_SCATTER_WPW 4
 #endif
 constexpr int SCATTER_WPW = PENGK_SCATTER_WPW;  // waves per workgroup of pass A
+// The one-level scheme (W = 8, 10) lets a full slice's keys overflow into the bucket-major table `temp` that pass B adds
+// its histograms to, at the index pass C reads: the final table is then written once, by pass C, and needs no clear.
+template <int W, int NBITS>
+struct KeySplitTemp : KeySplit<W, NBITS> {
+  __host__ __device__ static inline uint32_t join(uint32_t b, uint32_t p, uint32_t /*outer*/ = 0) { return (b << PAYLOAD_BITS) | p; }
+  __host__ __device__ static inline uint32_t index(uint32_t id) {
+    return (KeySplit<W, NBITS>::bucket(id) << PAYLOAD_BITS) | KeySplit<W, NBITS>::payload(id);
+  }
+};
 template <int W, bool BOTH, int NBITS, bool BG>
 __global__ __launch_bounds__(64 * SCATTER_WPW) void count_scatter_kernel(const uint32_t* __restrict__ words32,
                                                             const uint64_t* __restrict__ items, uint32_t n_items,
                                                             uint16_t* __restrict__ keys, uint32_t slice_cap,
-                                                            uint32_t* __restrict__ slice_fill, uint32_t* __restrict__ hist,
+                                                            uint32_t* __restrict__ slice_fill, uint32_t* __restrict__ temp,
                                                             unsigned long long* __restrict__ ltot,
-                                                            uint32_t* __restrict__ defer,
+                                                            uint32_t* __restrict__ defer_count,
+                                                            uint32_t* __restrict__ defer_list,
                                                             uint32_t* __restrict__ bg_partials) {
   static_assert(2 * W - NBITS == PAYLOAD_BITS, "payload must be 15 bits");
-  ScatterEmit<KeySplit<W, NBITS>, NBITS, SCATTER_WPW>::init_lds();
+  typedef ScatterEmit<KeySplitTemp<W, NBITS>, NBITS, SCATTER_WPW> Emit;
+  Emit::init_lds();
   bg_begin<BG>();
   __syncthreads();
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  ScatterEmit<KeySplit<W, NBITS>, NBITS, SCATTER_WPW> e{keys, slice_cap, slice_fill, hist, wave, threadIdx.x & 63u, blockIdx.x * (uint32_t)SCATTER_WPW + wave, 0u};
+  Emit e{keys, slice_cap, slice_fill, temp, wave, threadIdx.x & 63u, blockIdx.x * (uint32_t)SCATTER_WPW + wave, 0u};
   e.bind();
-  scan_items<W, BOTH, BG>(words32, items, n_items, ltot, defer, e);
+  scan_items<W, BOTH, BG>(words32, items, n_items, ltot, defer_count, defer_list, e);
   e.drain();
   bg_end<BG>(bg_partials);
 }
@@ -709,7 +736,7 @@ __global__ __launch_bounds__(64 * SCATTER12L1_WPW) void count_scatter12_kernel(c
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   Scatter12Emit e{keys, slice_cap, slice_fill, hist, wave, threadIdx.x & 63u, blockIdx.x * (uint32_t)SCATTER12L1_WPW + wave, 0u};
   e.bind();
-  scan_items<12, BOTH, BG>(words32, items, n_items, ltot, defer, e);
+  scan_items<12, BOTH, BG>(words32, items, n_items, ltot, defer, defer + 1, e);
   e.drain();
   bg_end<BG>(bg_partials);
 }
@@ -769,7 +796,7 @@ __global__ __launch_bounds__(64 * SCATTER12L1_WPW) void count_scatter14_kernel(c
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   Scatter14Emit e{keys, slice_cap, slice_fill, hist, wave, threadIdx.x & 63u, blockIdx.x * (uint32_t)SCATTER12L1_WPW + wave, 0u};
   e.bind();
-  scan_items<14, BOTH, BG>(words32, items, n_items, ltot, defer, e);
+  scan_items<14, BOTH, BG>(words32, items, n_items, ltot, defer, defer + 1, e);
   e.drain();
   bg_end<BG>(bg_partials);
 }
@@ -828,14 +855,14 @@ __global__ __launch_bounds__(256) void count_gather14_kernel(const uint32_t* __r
 }
 
 // One workgroup = 16 waves = part of one bucket: waves walk the (bucket, producer-wave) slices of their share.
-__global__ __launch_bounds__(1024) void count_hist_kernel(const uint16_t* __restrict__ keys, uint32_t slice_cap,
-                                                          uint32_t n_slices, uint32_t nb,
-                                                          const uint32_t* __restrict__ slice_fill, uint32_t bpb,
-                                                          uint32_t* __restrict__ temp, uint32_t slices_per_outer) {
-  extern __shared__ uint32_t h[];  // 2^15 bins
+// (`block`: the workgroup's index among those of pass B; h: its 2^15 bins in LDS)
+__device__ __forceinline__ void hist_block(uint32_t* __restrict__ h, uint32_t block, const uint16_t* __restrict__ keys,
+                                           uint32_t slice_cap, uint32_t n_slices, uint32_t nb,
+                                           const uint32_t* __restrict__ slice_fill, uint32_t bpb,
+                                           uint32_t* __restrict__ temp, uint32_t slices_per_outer) {
   // one level: fine bucket f = b, its slices are all producer waves.  Two levels (slices_per_outer > 0):
   // f = b1 * nb + b2, its slices are the producer waves of the level-2 workgroups that served b1.
-  const uint32_t f = blockIdx.x / bpb, j = blockIdx.x % bpb;
+  const uint32_t f = block / bpb, j = block % bpb;
   const uint32_t b = slices_per_outer ? f % nb : f;
   const uint32_t slice0 = slices_per_outer ? (f / nb) * slices_per_outer : 0u;
   if (slices_per_outer) n_slices = slices_per_outer;
@@ -890,6 +917,14 @@ __global__ __launch_bounds__(1024) void count_hist_kernel(const uint16_t* __rest
   }
 }
 
+__global__ __launch_bounds__(1024) void count_hist_kernel(const uint16_t* __restrict__ keys, uint32_t slice_cap,
+                                                          uint32_t n_slices, uint32_t nb,
+                                                          const uint32_t* __restrict__ slice_fill, uint32_t bpb,
+                                                          uint32_t* __restrict__ temp, uint32_t slices_per_outer) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t h[];  // 2^15 bins
+  hist_block(h, blockIdx.x, keys, slice_cap, n_slices, nb, slice_fill, bpb, temp, slices_per_outer);
+}
+
 // W = 12: table[id] += temp[bucket1 * 16 + bucket2][payload2]
 __global__ __launch_bounds__(256) void count_gather12_kernel(const uint32_t* __restrict__ temp, uint32_t* __restrict__ hist) {
   const uint32_t np = 1u << 24;
@@ -901,15 +936,17 @@ __global__ __launch_bounds__(256) void count_gather12_kernel(const uint32_t* __r
   }
 }
 
-// table[join(bucket, payload)] += temp[bucket][payload]
+// pass C of the one-level scheme: table[join(bucket, payload)] = temp[bucket][payload] -- everything counted went into
+// temp (pass B's histograms, overflowed slices, the fix-up), so the table is written, not added to, and needs no clear.
+// The first thread hands the window total accumulated beside temp to the caller.
 template <int W, int NBITS>
 __global__ __launch_bounds__(256) void count_gather_kernel(const uint32_t* __restrict__ temp, uint32_t np,
-                                                           uint32_t* __restrict__ hist) {
-  using KS = KeySplit<W, NBITS>;
-  for (uint32_t x = blockIdx.x * blockDim.x + threadIdx.x; x < np; x += gridDim.x * blockDim.x) {
-    const uint32_t v = temp[((size_t)KS::bucket(x) << PAYLOAD_BITS) | KS::payload(x)];
-    if (v) hist[x] += v;
-  }
+                                                           uint32_t* __restrict__ hist,
+                                                           const unsigned long long* __restrict__ ltot_acc,
+                                                           unsigned long long* __restrict__ ltot) {
+  using KS = KeySplitTemp<W, NBITS>;
+  if (blockIdx.x == 0 && threadIdx.x == 0) *ltot = *ltot_acc;
+  for (uint32_t x = blockIdx.x * blockDim.x + threadIdx.x; x < np; x += gridDim.x * blockDim.x) hist[x] = temp[KS::index(x)];
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -922,15 +959,16 @@ __device__ __forceinline__ uint32_t base_at(const uint32_t* __restrict__ words32
   return (words32[g >> 4] >> (2u * (uint32_t)(g & 15u))) & 3u;
 }
 
-__global__ __launch_bounds__(64) void count_fixup_kernel(const uint32_t* __restrict__ words32,
-                                                         const uint64_t* __restrict__ items, int W, int both,
-                                                         uint32_t* __restrict__ hist,
-                                                         const uint32_t* __restrict__ defer) {
-  const uint32_t n = defer[0];
+// lanes first, first + stride, .. of the n deferred items in `list`; ring(i): the lane's 16 ring slots; add(id)
+// counts one window
+template <class Ring, class Add>
+__device__ __forceinline__ void fixup_items(const uint32_t* __restrict__ words32, const uint64_t* __restrict__ items, int W,
+                                            int both, uint32_t n, const uint32_t* __restrict__ list, uint32_t first,
+                                            uint32_t stride, Ring ring, Add add) {
   const uint32_t mask = (1u << (2 * W)) - 1u;
   const int top = 2 * (W - 1);
-  for (uint32_t q = blockIdx.x * blockDim.x + threadIdx.x; q < n; q += gridDim.x * blockDim.x) {
-    const uint32_t it = defer[1 + q];
+  for (uint32_t q = first; q < n; q += stride) {
+    const uint32_t it = list[q];
     const uint64_t rec = items[it];
     const uint32_t nw = (uint32_t)((rec >> ITEM_NW_SHIFT) & ITEM_NW_MASK);
     const uint64_t ws = rec & ITEM_WS_MASK;
@@ -941,8 +979,7 @@ __global__ __launch_bounds__(64) void count_fixup_kernel(const uint32_t* __restr
     for (;;) {
       const uint64_t p0 = (ws - head > back) ? ws - back : head;
       bool certified = (p0 == head);
-      uint32_t ring[16];
-      for (int i = 0; i < 16; ++i) ring[i] = INVALID_ID;
+      for (int i = 0; i < 16; ++i) ring(i) = INVALID_ID;
       uint32_t id = 0, rc = 0;
       for (int b = 0; b < W - 1; ++b) {
         const uint32_t c = base_at(words32, p0 + b);
@@ -957,7 +994,7 @@ __global__ __launch_bounds__(64) void count_fixup_kernel(const uint32_t* __restr
         rc = ((rc << 2) & mask) | (c ^ 3u);
         const uint32_t can = both ? min(id, rc) : id;
         bool match = false;
-        for (int d = 1; d <= W - 1; ++d) match |= (ring[(uint32_t)(t - d) & 15u] == can);
+        for (int d = 1; d <= W - 1; ++d) match |= (ring((uint32_t)(t - d) & 15u) == can);
         if (t < ws) {
           clean = match ? 0u : clean + 1u;
           if (clean >= 2u * (uint32_t)(W - 1)) certified = true;
@@ -966,14 +1003,24 @@ __global__ __launch_bounds__(64) void count_fixup_kernel(const uint32_t* __restr
             ok = false;
             break;
           }
-          if (!match) __hip_atomic_fetch_add(&hist[can], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          if (!match) add(can);
         }
-        ring[(uint32_t)t & 15u] = match ? INVALID_ID : can;
+        ring((uint32_t)t & 15u) = match ? INVALID_ID : can;
       }
       if (ok) break;
       back *= 4ull;
     }
   }
+}
+
+__global__ __launch_bounds__(64) void count_fixup_kernel(const uint32_t* __restrict__ words32,
+                                                         const uint64_t* __restrict__ items, int W, int both,
+                                                         uint32_t* __restrict__ hist,
+                                                         const uint32_t* __restrict__ defer) {
+  uint32_t r[16];
+  fixup_items(words32, items, W, both, defer[0], defer + 1, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x,
+              [&](uint32_t i) -> uint32_t& { return r[i]; },
+              [&](uint32_t id) { __hip_atomic_fetch_add(&hist[id], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); });
 }
 
 // count[x] = count[revcomp(x)] for x > revcomp(x)  (src/base_pattern.cpp:387-392)
@@ -1069,13 +1116,15 @@ __global__ void bg_finish_kernel(const unsigned long long* __restrict__ raw, uns
   if (t < 64) out[20 + t] = raw[t];
 }
 
-// fused K1b: block partials (little-endian 3-mer digits) -> (n1 | n2 | n3) in BaMM order
-__global__ void bg_finish_fused_kernel(const uint32_t* __restrict__ partials, uint32_t n_blocks,
-                                       unsigned long long* __restrict__ out) {
-  __shared__ unsigned long long raw[84];
-  __shared__ unsigned long long n3[64];
-  __shared__ unsigned long long n2[16];
-  __shared__ unsigned long long part[12][84];
+// fused K1b: block partials (little-endian 3-mer digits) -> (n1 | n2 | n3) in BaMM order.  One workgroup of >= 1008
+// threads; lds: BG_FINISH_LDS 64-bit words.
+constexpr uint32_t BG_FINISH_LDS = 84 + 64 + 16 + 12 * 84;
+__device__ __forceinline__ void bg_finish_block(unsigned long long* __restrict__ lds, const uint32_t* __restrict__ partials,
+                                                uint32_t n_blocks, unsigned long long* __restrict__ out) {
+  unsigned long long* raw = lds;
+  unsigned long long* n3 = raw + 84;
+  unsigned long long* n2 = n3 + 64;
+  unsigned long long(*part)[84] = reinterpret_cast<unsigned long long(*)[84]>(n2 + 16);
   const int t = threadIdx.x;
   {  // 12 strands of 84 threads each sum every 12th block; fixed order -> deterministic
     const int bin = t % 84, strand = t / 84;
@@ -1122,6 +1171,45 @@ __global__ void bg_finish_fused_kernel(const uint32_t* __restrict__ partials, ui
     for (int b = 0; b < 4; ++b) s += n2[b * 4 + t];
     out[t] = s;
   }
+}
+
+__global__ __launch_bounds__(1024) void bg_finish_fused_kernel(const uint32_t* __restrict__ partials, uint32_t n_blocks,
+                                                               unsigned long long* __restrict__ out) {
+  __shared__ unsigned long long lds[BG_FINISH_LDS];
+  bg_finish_block(lds, partials, n_blocks, out);
+}
+
+// Pass B of the one-level scheme (W = 8, 10) with what else stands between pass A and pass C riding in front of its
+// grid: workgroup 0 folds the fused K1b's block partials (nothing in pass B needs them; alone in a launch it was a
+// one-workgroup kernel serialised in front of pass B), workgroups 1 .. n_fix redo the deferred items -- adding into
+// temp with the device-scope atomics pass B's own flush uses, which commute with it -- and the rest are pass B's.
+// Pass B is bound by HBM and needs one workgroup's LDS per CU; the few front workgroups borrow that LDS (rings of the
+// fix-up: 16 slots per thread, lane-strided, where the stand-alone kernel indexes a private array in scratch).
+template <int W, int NBITS>
+__global__ __launch_bounds__(1024) void count_hist_front_kernel(const uint16_t* __restrict__ keys, uint32_t slice_cap,
+                                                                uint32_t n_slices, const uint32_t* __restrict__ slice_fill,
+                                                                uint32_t bpb, uint32_t* __restrict__ temp,
+                                                                const uint32_t* __restrict__ bg_partials, uint32_t bg_blocks,
+                                                                unsigned long long* __restrict__ bg_out,
+                                                                const uint32_t* __restrict__ words32,
+                                                                const uint64_t* __restrict__ items, int both,
+                                                                const uint32_t* __restrict__ defer_count,
+                                                                const uint32_t* __restrict__ defer_list, uint32_t n_fix) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t h[];  // 2^15 bins
+  if (blockIdx.x == 0) {
+    if (bg_out) bg_finish_block(reinterpret_cast<unsigned long long*>(h), bg_partials, bg_blocks, bg_out);
+    return;
+  }
+  if (blockIdx.x <= n_fix) {
+    uint32_t* r = h + threadIdx.x;
+    fixup_items(words32, items, W, both, defer_count[0], defer_list, (blockIdx.x - 1u) * blockDim.x + threadIdx.x,
+                n_fix * blockDim.x, [&](uint32_t i) -> uint32_t& { return r[i * 1024u]; },
+                [&](uint32_t id) {
+                  __hip_atomic_fetch_add(&temp[KeySplitTemp<W, NBITS>::index(id)], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                });
+    return;
+  }
+  hist_block(h, blockIdx.x - 1u - n_fix, keys, slice_cap, n_slices, 1u << NBITS, slice_fill, bpb, temp, 0u);
 }
 
 // BackgroundModel::calculateV (src/shared/BackgroundModel.cpp:490-530), one thread, float32 in the
@@ -1259,6 +1347,7 @@ int launch_direct_w(pengk_ctx* ctx, int both, uint32_t* d_counts, uint64_t* d_lt
   return d_bg ? bg_finish_fused(ctx, blocks, d_bg) : PENGK_OK;
 }
 
+// W = 8, 10.  One clear and three kernels: launch_count leaves the defer counter, the table and ltot alone for this path.
 template <int W>
 int launch_partition_w(pengk_ctx* ctx, int both, uint32_t* d_counts, uint64_t* d_ltot, uint32_t n_items, uint64_t* d_bg) {
   constexpr int NBITS = 2 * W - PAYLOAD_BITS;
@@ -1284,14 +1373,19 @@ int launch_partition_w(pengk_ctx* ctx, int both, uint32_t* d_counts, uint64_t* d
   const uint32_t slice_cap = (uint32_t)cap64;
   int rc = ensure_scratch(ctx, &ctx->d_keys, &ctx->keys_bytes, (size_t)NB * n_waves * slice_cap * sizeof(uint16_t));
   if (rc) return rc;
+  // aux: slice fills | window total (64 bits), defer counter, pad | bucket-major table.  Only what lies behind the slice
+  // fills is cleared: drain() writes the fill of every (wave, bucket) of every launched wave, and pass B reads no other.
   const size_t fill_words = ((size_t)NB * n_waves + 63) / 64 * 64;
-  const size_t aux_need = fill_words * sizeof(uint32_t) + (size_t)np * sizeof(uint32_t);  // slice fills | bucket-major table
+  constexpr size_t HEAD_WORDS = 4;
+  const size_t aux_need = (fill_words + HEAD_WORDS + (size_t)np) * sizeof(uint32_t);
   rc = ensure_scratch(ctx, &ctx->d_count_aux, &ctx->count_aux_bytes, aux_need);
   if (rc) return rc;
   uint32_t* slice_fill = (uint32_t*)ctx->d_count_aux;
-  uint32_t* temp = slice_fill + fill_words;
-  PENGK_HIP(hipMemsetAsync(ctx->d_count_aux, 0, aux_need, ctx->stream));
-  unsigned long long* lt = (unsigned long long*)d_ltot;
+  unsigned long long* ltot_acc = (unsigned long long*)(slice_fill + fill_words);  // (fill_words: a multiple of 64)
+  uint32_t* defer_count = slice_fill + fill_words + 2;
+  uint32_t* temp = slice_fill + fill_words + HEAD_WORDS;
+  PENGK_HIP(hipMemsetAsync(ltot_acc, 0, (HEAD_WORDS + (size_t)np) * sizeof(uint32_t), ctx->stream));
+  ctx->d_defer_count = defer_count;
   uint16_t* keys = (uint16_t*)ctx->d_keys;
   uint32_t* bgp = nullptr;
   if (d_bg) {
@@ -1300,25 +1394,25 @@ int launch_partition_w(pengk_ctx* ctx, int both, uint32_t* d_counts, uint64_t* d
   }
 #define TA_SCATTER(B, G) W, B, NBITS, G
   PENGK_LAUNCH_BB(count_scatter_kernel, TA_SCATTER, both, d_bg != nullptr, dim3(blocks), dim3(TPB), w32, ctx->d_items, n_items,
-                  keys, slice_cap, slice_fill, d_counts, lt, ctx->d_defer, bgp);
+                  keys, slice_cap, slice_fill, temp, ltot_acc, defer_count, ctx->d_defer + 1, bgp);
 #undef TA_SCATTER
   PENGK_HIP(hipGetLastError());
-  if (d_bg) {
-    rc = bg_finish_fused(ctx, blocks, d_bg);
-    if (rc) return rc;
-  }
-  // pass B: one 1024-thread workgroup per CU (128 KiB of LDS), bpb workgroups per bucket
+  // pass B: one 1024-thread workgroup per CU (128 KiB of LDS), bpb workgroups per bucket; in front of them the
+  // workgroup that finishes the fused K1b and those of the fix-up (as many lanes as its stand-alone launch has)
   uint32_t bpb = ((uint32_t)ctx->num_cu * 2u + NB - 1) / NB;
   const uint64_t per_bucket = windows / NB + 1;
   const uint32_t useful = (uint32_t)((per_bucket + 65535) / 65536);  // >= 64 Ki keys per workgroup or it is not worth a block
   if (bpb > useful) bpb = useful;
   if (bpb > n_waves) bpb = n_waves;
   if (bpb < 1) bpb = 1;
-  hipLaunchKernelGGL(count_hist_kernel, dim3(NB * bpb), dim3(1024), 4 << PAYLOAD_BITS, ctx->stream, keys, slice_cap, n_waves,
-                     NB, slice_fill, bpb, temp, 0u);
+  constexpr uint32_t N_FIX = 4;
+  hipLaunchKernelGGL((count_hist_front_kernel<W, NBITS>), dim3(1u + N_FIX + NB * bpb), dim3(1024), 4 << PAYLOAD_BITS, ctx->stream,
+                     keys, slice_cap, n_waves, slice_fill, bpb, temp, bgp, blocks, (unsigned long long*)d_bg, w32, ctx->d_items, both,
+                     defer_count, ctx->d_defer + 1, N_FIX);
   PENGK_HIP(hipGetLastError());
   const uint32_t gb = (np + 255) / 256 < 2048u ? (np + 255) / 256 : 2048u;
-  hipLaunchKernelGGL((count_gather_kernel<W, NBITS>), dim3(gb), dim3(256), 0, ctx->stream, temp, np, d_counts);
+  hipLaunchKernelGGL((count_gather_kernel<W, NBITS>), dim3(gb), dim3(256), 0, ctx->stream, temp, np, d_counts, ltot_acc,
+                     (unsigned long long*)d_ltot);
   PENGK_HIP(hipGetLastError());
   return PENGK_OK;
 }
@@ -1502,8 +1596,8 @@ int launch_count_w(pengk_ctx* ctx, int both, uint32_t* d_counts, uint64_t* d_lto
     rc = impl == 2 ? launch_partition12(ctx, both, d_counts, d_ltot, n_items, d_bg)
                    : launch_direct_w<W>(ctx, both, d_counts, d_ltot, n_items, d_bg);
   } else if constexpr (can_partition) {
-    rc = impl == 2 ? launch_partition_w<W>(ctx, both, d_counts, d_ltot, n_items, d_bg)
-                   : launch_direct_w<W>(ctx, both, d_counts, d_ltot, n_items, d_bg);
+    if (impl == 2) return launch_partition_w<W>(ctx, both, d_counts, d_ltot, n_items, d_bg);  // (fix-up included)
+    rc = launch_direct_w<W>(ctx, both, d_counts, d_ltot, n_items, d_bg);
   } else {
     rc = launch_direct_w<W>(ctx, both, d_counts, d_ltot, n_items, d_bg);
   }
@@ -1519,6 +1613,8 @@ int launch_count_w(pengk_ctx* ctx, int both, uint32_t* d_counts, uint64_t* d_lto
 // hipFuncSetAttribute applies to the CURRENT device: called from pengk_create after hipSetDevice, once per context
 int count_init_device() {
   PENGK_HIP(hipFuncSetAttribute((const void*)count_hist_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 4 << PAYLOAD_BITS));
+  PENGK_HIP(hipFuncSetAttribute((const void*)count_hist_front_kernel<8, 16 - PAYLOAD_BITS>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 << PAYLOAD_BITS));
+  PENGK_HIP(hipFuncSetAttribute((const void*)count_hist_front_kernel<10, 20 - PAYLOAD_BITS>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 << PAYLOAD_BITS));
   return PENGK_OK;
 }
 
@@ -1535,9 +1631,15 @@ int launch_count(pengk_ctx* ctx, int both, uint32_t* d_counts, uint64_t* d_ltot,
       ctx->defer_cap = have / sizeof(uint32_t);
     }
   }
-  PENGK_HIP(hipMemsetAsync(ctx->d_defer, 0, sizeof(uint32_t), ctx->stream));
-  PENGK_HIP(hipMemsetAsync(d_counts, 0, np * sizeof(uint32_t), ctx->stream));
-  PENGK_HIP(hipMemsetAsync(d_ltot, 0, sizeof(uint64_t), ctx->stream));
+  // the one-level partition (W = 8, 10) keeps its counters beside its bucket-major table, clears them with it and
+  // writes every bin of the table: nothing to clear here
+  const bool one_level = (W == 8 || W == 10) && ctx->count_impl != 1 && ctx->n_items > 0;
+  if (!one_level) {
+    ctx->d_defer_count = ctx->d_defer;
+    PENGK_HIP(hipMemsetAsync(ctx->d_defer, 0, sizeof(uint32_t), ctx->stream));
+    PENGK_HIP(hipMemsetAsync(d_counts, 0, np * sizeof(uint32_t), ctx->stream));
+    PENGK_HIP(hipMemsetAsync(d_ltot, 0, sizeof(uint64_t), ctx->stream));
+  }
   switch (W) {
     case 2: return launch_count_w<2>(ctx, both, d_counts, d_ltot, d_bg);
     case 4: return launch_count_w<4>(ctx, both, d_counts, d_ltot, d_bg);

@@ -22,6 +22,7 @@ struct pengk_ctx {
   // scratch owned by the context
   uint32_t* d_defer = nullptr;  // deferred item indices + counter in slot 0
   uint64_t defer_cap = 0;
+  const uint32_t* d_defer_count = nullptr;  // where the last count kept its number of deferred items (d_defer or d_count_aux)
   double* d_em_partials = nullptr;
   size_t em_partials_bytes = 0;
   float* d_em_tables = nullptr;  // K5 fast mode: count*saturation | saturation*background, 4^W floats each
