@@ -505,6 +505,65 @@ int pengk_site_profiles(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t*
 int pengk_profile_refine(const uint64_t* h_counts, int w, int flank, const float* h_bg, double min_ic, double* h_q,
                          double* h_ic, float* h_pwm, int32_t* first_out, int32_t* last_out, uint64_t* sites_out);
 
+/* ---- motif pair spacing (--spacing: which pairs of found motifs occur in the same sequences more often than chance, and
+ *      whether they keep a fixed distance and orientation there; SpaMo's spacing histograms and binomial test, INTEGRATION.md
+ *      7g) ------------------------------------------------------------------------------------------------------------------
+ * Over the best sites of pengk_motif_best_sites.  Integer up to the summary: any slicing, any rank count and a numpy
+ * restatement give the same histograms. */
+#define PENGK_SPACING_MAX_MOTIFS 64
+#define PENGK_SPACING_MAX_GAP 1024
+/* Replaces SpaMo's per-sequence pairing of a primary and a secondary site.  The considered sequences are those with
+ * min_len <= L <= max_len (L = d_lens[i]; min_len at least every width, 1 <= max_len <= PENGK_CENTRALITY_MAX_LEN).  Motif m
+ * has a site in a considered sequence when its best score (d_best, d_site = 2p + s from pengk_motif_best_sites) is not
+ * PENGK_SCORE_SENTINEL, is >= h_thr[m] and p <= L - h_len[m]: ADDS 1 to d_hist_motifs[m].  For every pair a < b (pair
+ * index q = b (b - 1) / 2 + a) with sites (p_a, s_a), (p_b, s_b) in one sequence, with G = max_gap and B = 4 (G + 1) + 2
+ * bins per pair, ADDS 1 to d_hist_gaps[q * B + bin]:
+ *   the intervals [p_a, p_a + w_a) and [p_b, p_b + w_b) intersect                                bin 4 (G + 1)
+ *   else side = 0, g = p_b - p_a - w_a when p_b >= p_a + w_a; side = 1, g = p_a - p_b - w_b otherwise;
+ *   c = 2 (s_a ^ s_b) + (side ^ s_a)  (b on the other strand than a; b upstream of a read on a's strand)
+ *   g <= G: bin c (G + 1) + g;   g > G ("far"): bin 4 (G + 1) + 1
+ * and, unless they intersect, 1 to d_hist_lengths[q * (max_len + 1) + L].  Reverse-complementing a sequence changes no
+ * bin.  All three arrays uint64, caller-zeroed: slices and shards sum exactly.  n_seq = 0 or n_motifs = 0 does nothing;
+ * n_motifs = 1 fills d_hist_motifs only (the other two may be NULL).  At most PENGK_SPACING_MAX_MOTIFS motifs, max_gap
+ * <= PENGK_SPACING_MAX_GAP. */
+int pengk_spacing_histograms(pengk_ctx* ctx, int n_motifs, const int32_t* d_best, const uint64_t* d_site,
+                             const uint32_t* d_lens, uint64_t n_seq, const int32_t* h_len, const int32_t* h_thr,
+                             uint32_t max_gap, uint32_t min_len, uint32_t max_len,
+                             uint64_t* d_hist_gaps,    /* pairs x B */
+                             uint64_t* d_hist_lengths, /* pairs x (max_len + 1) */
+                             uint64_t* d_hist_motifs); /* n_motifs: n_m */
+typedef struct {
+  uint64_t both;            /* sequences with a site of either motif: overlapping + apart */
+  uint64_t overlapping;
+  uint64_t apart;           /* Na: not overlapping, far included */
+  uint64_t far;             /* of those: gap > max_gap */
+  double expected_both;     /* n * (n_a / n) * (n_b / n) */
+  double log10_pvalue_both; /* log10 P(X >= both), X ~ Binomial(n, (n_a / n) (n_b / n)) */
+  uint32_t orientation;     /* c of the reported bin: 0 same_downstream, 1 same_upstream, 2 opposite_downstream,
+                               3 opposite_upstream */
+  uint32_t gap;             /* g of the reported bin */
+  uint64_t count;           /* its sequences */
+  double expected;          /* Na * p(g) */
+  double log10_pvalue;      /* log10 P(X >= count), X ~ Binomial(Na, p(g)) */
+  double log10_evalue;      /* log10_pvalue + log10(n_classes * tested_gaps) + log10(n_pairs) */
+  uint32_t tested_gaps;     /* #{g <= max_gap : p(g) > 0}; 0: no bin was tested (Na = 0) and the six fields above are 0 */
+} pengk_spacing;
+/* Pure CPU.  Replaces SpaMo's binomial test.  One pair's test from its two histograms (h_gaps: B bins, h_lengths:
+ * max_len + 1 bins, as above, summed over the ranks), the widths, n_classes (2 with + scored only: c = 0, 1; else 4), the
+ * considered sequences n, those with a site of a and of b, and the pairs of the run (the Bonferroni factor).
+ * Co-occurrence: the margins taken as known rates, p_co = ((double)n_a / (double)n) * ((double)n_b / (double)n) -- an
+ * approximation (the exact test with fixed margins is hypergeometric).
+ * Gap: conditioned on the Na sequences where the two are apart.  Under independent uniform placement every (side, gap) of
+ * a sequence of length L has k(L, g) = max(0, L - w_a - w_b - g + 1) placements out of K(L) = T (T + 1) / 2, T = L - w_a -
+ * w_b + 1, and the classes are equally likely: p(g) = (1 / Na) * sum over ascending L of n_L * k(L, g) / (n_classes *
+ * K(L)), summed in double from 0.0, then one division.  For every c < n_classes and g <= max_gap with p(g) > 0: P(c, g) =
+ * P(X >= H[c][g]), X ~ Binomial(Na, p(g)).  Reported: the bin with the smallest log10 P, the smaller c, then the smaller
+ * g on ties.  Cost: one pass over the non-zero length bins per tested gap.  PENGK_ERR_ARG when the histograms disagree
+ * (different totals of apart sequences, a count in a class >= n_classes, a length below w_a + w_b, more than n_a, n_b). */
+int pengk_spacing_summary(const uint64_t* h_gaps /* B */, const uint64_t* h_lengths /* max_len + 1 */,
+                          uint32_t max_gap, uint32_t max_len, int w_a, int w_b, int n_classes /* 2 or 4 */,
+                          uint64_t n, uint64_t n_a, uint64_t n_b, int n_pairs, pengk_spacing* out);
+
 /* Self-test of the division sequence the serial EM's weights kernel uses where a PWM's operand ranges allow (the IEEE
  * division's instructions without its range scaling: csrc/em.hip, lean_div; src/peng.cpp:124-125, 186 are the three
  * divisions of a weight).  4096 x 256 threads draw pairs_per_thread random operand pairs each, keep those inside the

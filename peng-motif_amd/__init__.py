@@ -37,17 +37,28 @@ EXPORTS = [
     "pengk_sites_histograms", "pengk_sites_qvalues", "pengk_qvalue_threshold",
     "pengk_motif_best_sites", "pengk_centrality_histograms", "pengk_centrality_summary", "pengk_binomial_log10_sf",
     "pengk_site_profiles", "pengk_profile_refine",
+    "pengk_spacing_histograms", "pengk_spacing_summary",
 ]
 MAX_MOTIF_LEN = 64
 SCORE_SENTINEL = -2 ** 31
 SITES_BLOCK = 4096
 SITE = np.dtype([("seq", np.uint32), ("pos", np.uint32), ("score", np.int32), ("motif_strand", np.uint32)])
 CENTRALITY_MAX_LEN = 65536
+SPACING_MAX_MOTIFS = 64
+SPACING_MAX_GAP = 1024
+SPACING_CLASSES = ("same_downstream", "same_upstream", "opposite_downstream", "opposite_upstream")
 
 
 class CentralityStruct(C.Structure):
     _fields_ = [("sites", C.c_uint64), ("max_offset", C.c_uint32), ("window", C.c_uint32), ("in_window", C.c_uint64),
                 ("expected", C.c_double), ("log10_pvalue", C.c_double), ("log10_evalue", C.c_double)]
+
+
+class SpacingStruct(C.Structure):
+    _fields_ = [("both", C.c_uint64), ("overlapping", C.c_uint64), ("apart", C.c_uint64), ("far", C.c_uint64),
+                ("expected_both", C.c_double), ("log10_pvalue_both", C.c_double), ("orientation", C.c_uint32),
+                ("gap", C.c_uint32), ("count", C.c_uint64), ("expected", C.c_double), ("log10_pvalue", C.c_double),
+                ("log10_evalue", C.c_double), ("tested_gaps", C.c_uint32)]
 
 
 class PengkError(RuntimeError):
@@ -156,6 +167,9 @@ def lib():
         L.pengk_site_profiles.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, vp, vp, vp, vp, C.c_int, vp]
         L.pengk_profile_refine.argtypes = [vp, C.c_int, C.c_int, vp, C.c_double, vp, vp, vp, C.POINTER(C.c_int32),
                                            C.POINTER(C.c_int32), C.POINTER(u64)]
+        L.pengk_spacing_histograms.argtypes = [vp, C.c_int, vp, vp, vp, u64, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp]
+        L.pengk_spacing_summary.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, u64, u64, u64, C.c_int,
+                                            C.POINTER(SpacingStruct)]
         _lib = L
     return _lib
 
@@ -271,6 +285,18 @@ def binomial_log10_sf(n, k, p):
     out = C.c_double()
     _check(lib().pengk_binomial_log10_sf(int(n), int(k), float(p), C.byref(out)))
     return out.value
+
+
+def spacing_summary(hist_gaps, hist_lengths, max_gap, max_len, w_a, w_b, n_classes, n, n_a, n_b, n_pairs):
+    """one motif pair's co-occurrence and gap test from its two histograms (pengk_spacing_summary, CPU): a dict with the
+    fields of pengk_spacing"""
+    hg = np.ascontiguousarray(hist_gaps, np.uint64)
+    hl = np.ascontiguousarray(hist_lengths, np.uint64)
+    assert len(hg) == 4 * (max_gap + 1) + 2 and len(hl) == max_len + 1
+    out = SpacingStruct()
+    _check(lib().pengk_spacing_summary(hg.ctypes.data, hl.ctypes.data, max_gap, max_len, w_a, w_b, n_classes, int(n), int(n_a),
+                                       int(n_b), n_pairs, C.byref(out)))
+    return {k: getattr(out, k) for k, _ in SpacingStruct._fields_}
 
 
 def clamp_flank(w, flank):
@@ -677,6 +703,24 @@ class Context:
         _check(lib().pengk_centrality_histograms(self.h, n, _ptr(best), _ptr(site), _ptr(lens_dev), n_seq, w.ctypes.data,
                                                  th.ctypes.data, max_len, _ptr(hd), _ptr(hl)))
         return hd, hl
+
+    # ---- motif pair spacing (--spacing) ----------------------------------------------------------------------------
+    def spacing_histograms(self, best, site, lens_dev, n_seq, widths, thr, max_gap, min_len, max_len, hg=None, hl=None, hm=None):
+        """(hg, hl, hm) device uint64: pairs x (4 (max_gap + 1) + 2) gap bins, pairs x (max_len + 1) length bins (pair
+        b (b - 1) / 2 + a, a < b) and the n_motifs site counts, ADDED to (allocated zeroed if None)"""
+        n = len(widths)
+        pairs = n * (n - 1) // 2
+        w = np.ascontiguousarray(widths, np.int32)
+        th = np.ascontiguousarray(thr, np.int32)
+        if hg is None:
+            hg = self.to_device(np.zeros((max(pairs, 1), 4 * (max_gap + 1) + 2), np.uint64))
+        if hl is None:
+            hl = self.to_device(np.zeros((max(pairs, 1), max_len + 1), np.uint64))
+        if hm is None:
+            hm = self.to_device(np.zeros(max(n, 1), np.uint64))
+        _check(lib().pengk_spacing_histograms(self.h, n, _ptr(best), _ptr(site), _ptr(lens_dev), n_seq, w.ctypes.data,
+                                              th.ctypes.data, max_gap, min_len, max_len, _ptr(hg), _ptr(hl), _ptr(hm)))
+        return hg, hl, hm
 
     # ---- motif refinement (--refine) ---------------------------------------------------------------------------
     def site_profiles(self, scan, best, site, widths, thr, flank, counts=None):

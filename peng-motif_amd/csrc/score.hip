@@ -586,6 +586,127 @@ __global__ __launch_bounds__(HIST_THREADS) void centrality_hist_kernel(const int
   }
 }
 
+// ---- motif pair spacing (pengk_spacing_histograms) ---------------------------------------------------
+constexpr int SPACE_THREADS = 1024;
+constexpr int SPACE_LDS_BINS = 16000;  // the bins of one row's pairs in LDS (62.5 KiB, two workgroups per CU)
+
+// a grid row: motif b against the motifs [a0, a1) before it; the row with a0 = 0 also counts b's own sites
+struct SpaceRow {
+  int32_t b, a0, a1, pad;
+};
+
+// One more in bin `bin` of h for every lane with `on`; every lane of the wave calls.  The lanes that share the first
+// counting lane's bin add once, together: a composite element sends nearly every lane to one gap bin and equal-length
+// input sends every lane to one length bin, where 64 adds to one LDS address would queue.  The others add on their own.
+__device__ __forceinline__ void wave_count(uint32_t* h, bool on, uint32_t bin) {
+  const unsigned long long act = __ballot(on);
+  if (!act) return;
+  const int lead = __ffsll(act) - 1;
+  const uint32_t first = (uint32_t)__shfl((int)bin, lead);
+  const unsigned long long same = __ballot(on && bin == first);
+  if (!on) return;
+  if (bin != first) atomicAdd(&h[bin], 1u);
+  else if ((int)(threadIdx.x & 63u) == lead) atomicAdd(&h[first], (uint32_t)__popcll(same));
+}
+
+// per row (blockIdx.y): motif b's site read once per sequence and, only where b has one, the motifs a of the row: best[a]
+// first, site[a] on a hit.  wt: (width, threshold) per motif.  Considered: min_len <= L <= max_len.  Pair q = b (b - 1) / 2
+// + a owns nb = 4 (G + 1) + 2 gap bins in hg and max_len + 1 length bins in hl (include/pengk.h, "motif pair spacing").
+// LDS: the row's (a1 - a0) (nb + max_len + 1) bins in LDS as uint32, flushed once per block, one add per non-zero bin.
+template <bool LDS>
+__global__ __launch_bounds__(SPACE_THREADS) void spacing_hist_kernel(const int32_t* __restrict__ best,
+                                                                     const unsigned long long* __restrict__ site,
+                                                                     const uint32_t* __restrict__ lens, uint64_t n_seq,
+                                                                     const int32_t* __restrict__ wt,
+                                                                     const SpaceRow* __restrict__ rows, uint32_t G,
+                                                                     uint32_t min_len, uint32_t max_len,
+                                                                     unsigned long long* __restrict__ hg,
+                                                                     unsigned long long* __restrict__ hl,
+                                                                     unsigned long long* __restrict__ hm) {
+  __shared__ uint32_t h[LDS ? SPACE_LDS_BINS : 1];
+  __shared__ int32_t sw[PENGK_SPACING_MAX_MOTIFS], st[PENGK_SPACING_MAX_MOTIFS];
+  __shared__ unsigned long long s_sites;
+  const SpaceRow row = rows[blockIdx.y];
+  const uint32_t nb = 4 * (G + 1) + 2, nl = max_len + 1, per = nb + nl;
+  const uint32_t n_lds = (uint32_t)(row.a1 - row.a0) * per;  // (LDS only: the host made it fit)
+  if (threadIdx.x < (unsigned)row.a1 || (int)threadIdx.x == row.b) {
+    sw[threadIdx.x] = wt[2 * threadIdx.x];
+    st[threadIdx.x] = wt[2 * threadIdx.x + 1];
+  }
+  if (threadIdx.x == 0) s_sites = 0;
+  if (LDS)
+    for (uint32_t k = threadIdx.x; k < n_lds; k += SPACE_THREADS) h[k] = 0;
+  __syncthreads();
+  const uint32_t wb = (uint32_t)sw[row.b];
+  const int32_t tb = st[row.b];
+  const int32_t* Bb = best + (uint64_t)row.b * n_seq;
+  const unsigned long long* Cb = site + (uint64_t)row.b * n_seq;
+  const uint64_t q0 = (uint64_t)row.b * (uint64_t)(row.b - 1) / 2;  // (b = 0: no pair, never used)
+  uint32_t mine = 0;  // b's sites seen by this thread (a block walks fewer than 2^32 sequences: the host sees to it)
+  // (the loop's trip count is the same for every lane of a wave: wave_count needs them all)
+  for (uint64_t i0 = blockIdx.x * (uint64_t)SPACE_THREADS; i0 < n_seq; i0 += (uint64_t)gridDim.x * SPACE_THREADS) {
+    const uint64_t i = i0 + threadIdx.x;
+    bool has = false;
+    uint32_t L = 0, pb = 0, sb = 0;
+    if (i < n_seq) {
+      L = lens[i];
+      if (L >= min_len && L <= max_len) {
+        const int32_t s = Bb[i];
+        if (s != PENGK_SCORE_SENTINEL && s >= tb) {
+          const unsigned long long c = Cb[i];
+          has = (c >> 1) <= (unsigned long long)(L - wb);
+          pb = (uint32_t)(c >> 1);
+          sb = (uint32_t)(c & 1u);
+        }
+      }
+    }
+    mine += has;
+    if (!__any(has)) continue;
+    for (int a = row.a0; a < row.a1; ++a) {
+      bool apart = false, hit = false;
+      uint32_t bin = 0;
+      if (has) {
+        const int32_t s = best[(uint64_t)a * n_seq + i];
+        if (s != PENGK_SCORE_SENTINEL && s >= st[a]) {
+          const unsigned long long c = site[(uint64_t)a * n_seq + i];
+          const uint32_t wa = (uint32_t)sw[a], sa = (uint32_t)(c & 1u);
+          if ((c >> 1) <= (unsigned long long)(L - wa)) {
+            const uint32_t pa = (uint32_t)(c >> 1);
+            hit = true;
+            if (pb >= pa + wa || pa >= pb + wb) {
+              apart = true;
+              const uint32_t side = pb >= pa + wa ? 0u : 1u;
+              const uint32_t g = side ? pa - pb - wb : pb - pa - wa;
+              bin = g <= G ? (2 * (sa ^ sb) + (side ^ sa)) * (G + 1) + g : nb - 1;
+            } else {
+              bin = nb - 2;
+            }
+          }
+        }
+      }
+      if (LDS) {
+        uint32_t* hp = h + (uint32_t)(a - row.a0) * per;
+        wave_count(hp, hit, bin);
+        wave_count(hp + nb, apart, L);
+      } else if (hit) {
+        const uint64_t q = q0 + (uint64_t)a;
+        atomicAdd(&hg[q * nb + bin], 1ull);
+        if (apart) atomicAdd(&hl[q * nl + L], 1ull);
+      }
+    }
+  }
+  if (row.a0 == 0 && mine) atomicAdd(&s_sites, (unsigned long long)mine);
+  __syncthreads();
+  if (row.a0 == 0 && threadIdx.x == 0 && s_sites) atomicAdd(&hm[row.b], s_sites);
+  if (LDS)
+    for (uint32_t k = threadIdx.x; k < n_lds; k += SPACE_THREADS)
+      if (h[k]) {
+        const uint32_t slot = k / per, r = k - slot * per;
+        const uint64_t q = q0 + (uint64_t)row.a0 + slot;
+        atomicAdd(r < nb ? &hg[q * nb + r] : &hl[q * nl + (r - nb)], (unsigned long long)h[k]);
+      }
+}
+
 // ---- site profiles (pengk_site_profiles) -------------------------------------------------------------
 constexpr int PROF_THREADS = 256;
 constexpr int PROF_BINS = PENGK_MAX_MOTIF_LEN * 5;
@@ -1524,6 +1645,139 @@ int pengk_centrality_summary(const uint64_t* h_hist_offsets, const uint64_t* h_h
     }
   }
   out->log10_evalue = out->log10_pvalue + std::log10((double)(Dm + 1)) + std::log10((double)n_motifs);
+  return PENGK_OK;
+}
+
+int pengk_spacing_histograms(pengk_ctx* ctx, int n_motifs, const int32_t* d_best, const uint64_t* d_site,
+                             const uint32_t* d_lens, uint64_t n_seq, const int32_t* h_len, const int32_t* h_thr,
+                             uint32_t max_gap, uint32_t min_len, uint32_t max_len, uint64_t* d_hist_gaps,
+                             uint64_t* d_hist_lengths, uint64_t* d_hist_motifs) {
+  if (!ctx || n_motifs < 0 || (n_motifs && (!h_len || !h_thr || !d_hist_motifs)) ||
+      (n_motifs > 1 && (!d_hist_gaps || !d_hist_lengths)) || (n_seq && n_motifs && (!d_best || !d_site || !d_lens)))
+    return fail(PENGK_ERR_ARG, "pengk_spacing_histograms: bad argument");
+  if (n_motifs > PENGK_SPACING_MAX_MOTIFS)
+    return fail(PENGK_ERR_ARG, "pengk_spacing_histograms: %d motifs (at most %d)", n_motifs, PENGK_SPACING_MAX_MOTIFS);
+  if (max_gap > PENGK_SPACING_MAX_GAP)
+    return fail(PENGK_ERR_ARG, "pengk_spacing_histograms: max_gap %u (at most %d)", max_gap, PENGK_SPACING_MAX_GAP);
+  if (max_len < 1 || max_len > PENGK_CENTRALITY_MAX_LEN)
+    return fail(PENGK_ERR_ARG, "pengk_spacing_histograms: max_len %u (1..%d)", max_len, PENGK_CENTRALITY_MAX_LEN);
+  for (int m = 0; m < n_motifs; ++m) {
+    if (h_len[m] < 1 || h_len[m] > PENGK_MAX_MOTIF_LEN)
+      return fail(PENGK_ERR_ARG, "pengk_spacing_histograms: motif %d has width %d (1..%d)", m, h_len[m], PENGK_MAX_MOTIF_LEN);
+    if (min_len < (uint32_t)h_len[m])
+      return fail(PENGK_ERR_ARG, "pengk_spacing_histograms: min_len %u below the width %d of motif %d", min_len, h_len[m], m);
+  }
+  SCORE_ENTER(ctx);
+  if (n_seq == 0 || n_motifs == 0) return PENGK_OK;
+  // LDS bins when a pair's bins fit and the input is large enough for a block to add to a bin more than once; a motif
+  // with more earlier motifs than fit gets several rows.  Else one row per motif, global bins.
+  const uint64_t per = 4ull * (max_gap + 1) + 2 + (uint64_t)max_len + 1;
+  const bool lds = per <= (uint64_t)SPACE_LDS_BINS && n_seq >= (uint64_t)SPACE_THREADS * 16;
+  const int fit = lds ? (int)((uint64_t)SPACE_LDS_BINS / per) : PENGK_SPACING_MAX_MOTIFS;
+  std::vector<SpaceRow> rows;
+  for (int b = 0; b < n_motifs; ++b)
+    for (int a0 = 0; a0 == 0 || a0 < b; a0 += fit) rows.push_back(SpaceRow{b, a0, std::min(b, a0 + fit), 0});
+  const size_t wb = 2 * (size_t)n_motifs * sizeof(int32_t);  // (a multiple of 8: the rows are 16 bytes each)
+  std::vector<char> staged(wb + rows.size() * sizeof(SpaceRow));
+  int32_t* wt = (int32_t*)staged.data();
+  for (int m = 0; m < n_motifs; ++m) {
+    wt[2 * m] = h_len[m];
+    wt[2 * m + 1] = h_thr[m];
+  }
+  memcpy(staged.data() + wb, rows.data(), rows.size() * sizeof(SpaceRow));
+  int rc = ensure_scratch(ctx, &ctx->d_misc, &ctx->misc_bytes, staged.size());
+  if (rc) return rc;
+  PENGK_HIP(hipStreamSynchronize(ctx->stream));
+  PENGK_HIP(hipMemcpy(ctx->d_misc, staged.data(), staged.size(), hipMemcpyHostToDevice));
+  // blocks per row: four per CU over all rows, and enough that no block's uint32 bin can wrap
+  const uint64_t blocks = (n_seq + SPACE_THREADS - 1) / SPACE_THREADS;
+  const uint64_t per_row = std::max<uint64_t>(std::min<uint64_t>(blocks, (uint64_t)ctx->num_cu * 4 / rows.size() + 1), (n_seq >> 31) + 1);
+  const dim3 grid((unsigned)per_row, (unsigned)rows.size());
+  const int32_t* d_wt = (const int32_t*)ctx->d_misc;
+  const SpaceRow* d_rows = (const SpaceRow*)((const char*)ctx->d_misc + wb);
+  const unsigned long long* site = (const unsigned long long*)d_site;
+  unsigned long long* hg = (unsigned long long*)d_hist_gaps;
+  unsigned long long* hl = (unsigned long long*)d_hist_lengths;
+  unsigned long long* hm = (unsigned long long*)d_hist_motifs;
+  if (lds)
+    hipLaunchKernelGGL(spacing_hist_kernel<true>, grid, dim3(SPACE_THREADS), 0, ctx->stream, d_best, site, d_lens, n_seq, d_wt,
+                       d_rows, max_gap, min_len, max_len, hg, hl, hm);
+  else
+    hipLaunchKernelGGL(spacing_hist_kernel<false>, grid, dim3(SPACE_THREADS), 0, ctx->stream, d_best, site, d_lens, n_seq, d_wt,
+                       d_rows, max_gap, min_len, max_len, hg, hl, hm);
+  PENGK_HIP(hipGetLastError());
+  return PENGK_OK;
+}
+
+int pengk_spacing_summary(const uint64_t* h_gaps, const uint64_t* h_lengths, uint32_t max_gap, uint32_t max_len, int w_a,
+                          int w_b, int n_classes, uint64_t n, uint64_t n_a, uint64_t n_b, int n_pairs, pengk_spacing* out) {
+  if (!h_gaps || !h_lengths || !out || max_gap > PENGK_SPACING_MAX_GAP || max_len < 1 || max_len > PENGK_CENTRALITY_MAX_LEN ||
+      w_a < 1 || w_a > PENGK_MAX_MOTIF_LEN || w_b < 1 || w_b > PENGK_MAX_MOTIF_LEN || (n_classes != 2 && n_classes != 4) ||
+      n_a > n || n_b > n || n_pairs < 1)
+    return fail(PENGK_ERR_ARG, "pengk_spacing_summary: bad argument");
+  memset(out, 0, sizeof *out);
+  const uint32_t G1 = max_gap + 1;
+  uint64_t near = 0;
+  for (uint32_t k = 0; k < 4 * G1; ++k) {
+    if (h_gaps[k] && (int)(k / G1) >= n_classes)
+      return fail(PENGK_ERR_ARG, "pengk_spacing_summary: a count in orientation %u of %d", k / G1, n_classes);
+    near += h_gaps[k];
+  }
+  out->overlapping = h_gaps[4 * G1];
+  out->far = h_gaps[4 * G1 + 1];
+  out->apart = near + out->far;
+  out->both = out->overlapping + out->apart;
+  if (out->both > n_a || out->both > n_b) return fail(PENGK_ERR_ARG, "pengk_spacing_summary: more pairs than sites of a motif");
+  // the apart sequences' lengths, ascending
+  const int64_t ws = (int64_t)w_a + w_b;
+  std::vector<uint32_t> Ls;
+  uint64_t nl = 0;
+  for (uint32_t L = 0; L <= max_len; ++L) {
+    if (!h_lengths[L]) continue;
+    if ((int64_t)L < ws) return fail(PENGK_ERR_ARG, "pengk_spacing_summary: two sites apart on a sequence shorter than both motifs");
+    nl += h_lengths[L];
+    Ls.push_back(L);
+  }
+  if (nl != out->apart) return fail(PENGK_ERR_ARG, "pengk_spacing_summary: the histograms hold different totals");
+  if (n) {
+    const double p_co = ((double)n_a / (double)n) * ((double)n_b / (double)n);
+    out->expected_both = (double)n * p_co;
+    out->log10_pvalue_both = log10_binomial_sf(n, out->both, p_co);
+  }
+  const uint64_t Na = out->apart;
+  if (Na == 0) return PENGK_OK;
+  std::vector<double> pg(G1, 0.0);
+  for (uint32_t g = 0; g <= max_gap; ++g) {
+    double s = 0.0;
+    for (const uint32_t L : Ls) {
+      const int64_t T = (int64_t)L - ws + 1, k = T - (int64_t)g;
+      if (k > 0) s += (double)h_lengths[L] * (double)k / ((double)n_classes * (double)(T * (T + 1) / 2));
+    }
+    pg[g] = s / (double)Na;
+    if (pg[g] > 0.0) {
+      ++out->tested_gaps;
+      continue;
+    }
+    for (int c = 0; c < n_classes; ++c)
+      if (h_gaps[(uint32_t)c * G1 + g]) return fail(PENGK_ERR_ARG, "pengk_spacing_summary: gap %u on sequences too short for it", g);
+  }
+  bool have = false;
+  for (int c = 0; c < n_classes; ++c)
+    for (uint32_t g = 0; g <= max_gap; ++g) {
+      if (!(pg[g] > 0.0)) continue;
+      const uint64_t H = h_gaps[(uint32_t)c * G1 + g];
+      const double lp = log10_binomial_sf(Na, H, std::min(1.0, pg[g]));
+      if (!have || lp < out->log10_pvalue) {
+        have = true;
+        out->orientation = (uint32_t)c;
+        out->gap = g;
+        out->count = H;
+        out->expected = (double)Na * pg[g];
+        out->log10_pvalue = lp;
+      }
+    }
+  out->log10_evalue =
+      out->log10_pvalue + std::log10((double)n_classes * (double)out->tested_gaps) + std::log10((double)n_pairs);
   return PENGK_OK;
 }
 

@@ -55,14 +55,18 @@ double Global::refinePvalue = 1e-4;
 int Global::refineFlank = 8;
 int Global::refineIterations = 3;
 double Global::refineMinIC = 0.25;
+char* Global::spacingFilename = nullptr;
+double Global::spacingPvalue = 1e-4;
+int Global::spacingMaxGap = 150;
+int Global::spacingMotifs = 16;
 
 void Global::init(int nargs, char* args[]) {
   readArguments(nargs, args);
   Alphabet::init(alphabetType);
   pengk_host::start_context();  // the device runtime starts while the FASTA files are read
   pengk_host::start_sharded_ingest();  // multi-GPU run: every rank reads its own byte range of the files
-  // (the scoring, the sites, the centrality and the refinement scan the input after the motifs are found)
-  pengk_host::keep_host_codes(scoreMotifs || sitesFilename || centralityFilename || refineFilename);
+  // (the scoring, the sites, the centrality, the refinement and the spacing scan the input after the motifs are found)
+  pengk_host::keep_host_codes(scoreMotifs || sitesFilename || centralityFilename || refineFilename || spacingFilename);
   // both strands are handled inside the count; sequences are always read single stranded
   // ... and every chunk of the input set is packed and sent to the device while the rest is still being read
   pengk_host::begin_streaming_pack(patternLength);
@@ -269,6 +273,28 @@ void Global::readArguments(int nargs, char* args[]) {
         log_line("ERROR", "--refine-min-ic must be a number of bits in [0, 2]");
         exit(4);
       }
+    } else if (!strcmp(a, "--spacing")) {
+      spacingFilename = (char*)need(i, nargs, args, printHelp);
+    } else if (!strcmp(a, "--spacing-pvalue")) {
+      const char* v = need(i, nargs, args, printHelp);
+      char* end = nullptr;
+      spacingPvalue = std::strtod(v, &end);
+      if (end == v || *end || !(spacingPvalue > 0.0 && spacingPvalue <= 1.0)) {
+        printHelp();
+        log_line("ERROR", "--spacing-pvalue must be a number in (0, 1]");
+        exit(4);
+      }
+    } else if (!strcmp(a, "--spacing-max-gap") || !strcmp(a, "--spacing-motifs")) {
+      const bool gap = a[11] == 'a';
+      const char* v = need(i, nargs, args, printHelp);
+      char* end = nullptr;
+      const long n = std::strtol(v, &end, 10);
+      if (end == v || *end || n < (gap ? 0 : 2) || n > (gap ? PENGK_SPACING_MAX_GAP : PENGK_SPACING_MAX_MOTIFS)) {
+        printHelp();
+        log_line("ERROR", gap ? "--spacing-max-gap must be an integer in [0, 1024]" : "--spacing-motifs must be an integer in [2, 64]");
+        exit(4);
+      }
+      (gap ? spacingMaxGap : spacingMotifs) = (int)n;
     } else if (!strcmp(a, "--version")) {
       std::cout << "peng_motif " << VERSION_NUMBER << std::endl;  // (src/Global.cpp:299-301: without the word)
       exit(0);
@@ -327,6 +353,12 @@ void Global::printHelp() {
   printf("  --refine-flank INT             columns looked at on either side of a motif (default 8)\n");
   printf("  --refine-iterations INT        at most this many rounds of sites -> matrix (default 3)\n");
   printf("  --refine-min-ic FLOAT          information (bits) an outermost kept column needs (default 0.25)\n");
+  printf("  --spacing FILE                 test every pair of motifs for co-occurrence in the same sequences and for a\n");
+  printf("                                 preferred gap and orientation (TSV: best site per sequence at p-value\n");
+  printf("                                 --spacing-pvalue or below, binomial tests)\n");
+  printf("  --spacing-pvalue FLOAT         p-value threshold of a best site, in (0, 1] (default 1e-4)\n");
+  printf("  --spacing-max-gap INT          largest gap between two sites that gets a bin of its own, 0..1024 (default 150)\n");
+  printf("  --spacing-motifs INT           only the first INT motifs take part, 2..64 (default 16)\n");
   printf("  --threads INT                  accepted for compatibility\n");
   printf("  --device INT                   HIP device index (default 0)\n");
   printf("  -v INT                         verbosity\n");

@@ -70,6 +70,10 @@ class Global {
   static int refineFlank;                    // --refine-flank
   static int refineIterations;               // --refine-iterations
   static double refineMinIC;                 // --refine-min-ic
+  static char* spacingFilename;              // --spacing (new: co-occurrence and preferred gap of motif pairs)
+  static double spacingPvalue;               // --spacing-pvalue
+  static int spacingMaxGap;                  // --spacing-max-gap
+  static int spacingMotifs;                  // --spacing-motifs
 
   static void init(int nargs, char* args[]);
   static void destruct();

@@ -16,6 +16,7 @@
 #include "motif_score.h"
 #include "motif_centrality.h"
 #include "motif_refine.h"
+#include "motif_spacing.h"
 #include "motif_sites.h"
 #include "peng.h"
 
@@ -105,9 +106,9 @@ int main(int nargs, char** args) {
   clock.lap("process (count, sweep, hill-climb, PWMs, EM, merging)");
   peng.filter_redundancy(Global::mergeBitfactorThreshold, result);
   std::vector<MotifScore> scores;
-  // (the scoring, the sites, the centrality and the refinement share one scan layout of the input)
+  // (the scoring, the sites, the centrality, the refinement and the spacing share one scan layout of the input)
   std::unique_ptr<ScanInput> scan;
-  if (Global::scoreMotifs || Global::sitesFilename || Global::centralityFilename || Global::refineFilename) {
+  if (Global::scoreMotifs || Global::sitesFilename || Global::centralityFilename || Global::refineFilename || Global::spacingFilename) {
     scan.reset(new ScanInput);
     build_scan_input(*Global::inputSequenceSet, scan.get());
   }
@@ -132,7 +133,7 @@ int main(int nargs, char** args) {
   const std::vector<MotifScore>* sc = Global::scoreMotifs ? &scores : nullptr;
   // the MEME file's order: as it is, or as the writers sort it (the same sort of the same vector: the same order)
   std::vector<IUPACPattern*> meme_order(result);
-  if (!sc && (Global::sitesFilename || Global::centralityFilename || Global::refineFilename))
+  if (!sc && (Global::sitesFilename || Global::centralityFilename || Global::refineFilename || Global::spacingFilename))
     std::sort(meme_order.begin(), meme_order.end(), sort_IUPAC_patterns);
   if (Global::sitesFilename) {
     write_motif_sites(meme_order, *Global::inputSequenceSet, *scan, *bgModel, Global::strand == Strand::BOTH_STRANDS,
@@ -153,6 +154,11 @@ int main(int nargs, char** args) {
     write_refined_motifs(meme_order, *Global::inputSequenceSet, *scan, *bgModel, Global::strand == Strand::BOTH_STRANDS, rs,
                          Global::refineFilename);
     clock.lap("refine");
+  }
+  if (Global::spacingFilename) {
+    write_motif_spacing(meme_order, *Global::inputSequenceSet, *scan, *bgModel, Global::strand == Strand::BOTH_STRANDS,
+                        Global::spacingPvalue, Global::spacingMaxGap, Global::spacingMotifs, Global::spacingFilename);
+    clock.lap("spacing");
   }
   scan.reset();
   if (pengk_host::rank() == 0) {
