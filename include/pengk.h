@@ -347,6 +347,31 @@ int pengk_synth_scan_sequences(pengk_ctx* ctx, uint64_t seed, uint64_t seq0, uin
  * conditional probability of bases 0..b.  seq0 makes shards of a multi-process run sample what one process samples. */
 int pengk_sample_background(pengk_ctx* ctx, uint64_t seed, uint64_t seq0, uint64_t n_seq, const int64_t* d_offs,
                             const uint32_t* d_lens, int K, const uint32_t* h_thresholds, uint64_t* d_words);
+/* Dinucleotide-preserving shuffle (--score-negatives shuffled): one negative per input sequence with the sequence's own
+ * 25 doublet counts, first and last letter, uniform over all such sequences (Altschul and Erickson 1985; uShuffle's
+ * construction without edge lists).  Input and output in the scan layout above with the same d_offs / d_lens; every
+ * sequence owns its words.  The definition, which a numpy restatement and any sharding reproduce bit for bit:
+ *   letters   a = 0..3 (A,C,G,T) where the validity bit is 1, a = 4 where it is 0: runs of other letters keep their
+ *             neighbourhoods and the negative gets validity bits of its own.  Sequence g = seq0 + i, letters
+ *             s[0..L-1], L < 2^31.
+ *   counts    cnt[u][v] = #{p in 0..L-2: s[p] = u, s[p+1] = v}, out[u] = sum_v cnt[u][v], f = s[L-1]
+ *   draws     draw(c) = mix64(seed + 0x9E3779B97F4A7C15 * ((g << 32) + c)) >> 32 (mod 2^64; mix64 = the splitmix64
+ *             finalizer); pick(c, n) = (draw(c) * n) >> 32 as a 64-bit product, 0 <= pick < n (its bias of at most
+ *             n / 2^32 is part of the definition); sel(u, k) = the smallest v with cnt[u][0] + .. + cnt[u][v] > k
+ *   tree      the last edge of every letter, a uniform arborescence into f by Wilson's loop-erased walk: in_tree = {f},
+ *             t = 0; for u0 = 0..4 in this order, unless out[u0] = 0 or u0 is in the tree: u = u0; while u is not in
+ *             the tree { v = sel(u, pick(2^31 + t, out[u])); t += 1; next[u] = v; u = v }; then u = u0; while u is
+ *             not in the tree { add u; u = next[u] }
+ *   reserve   for every u != f with out[u] > 0: cnt[u][next[u]] -= 1, rem[u] = out[u] - 1; rem[f] = out[f]
+ *   walk      o[0] = s[0], u = o[0]; for p = 1..L-1: if rem[u] > 0 { v = sel(u, pick(p, rem[u])); cnt[u][v] -= 1;
+ *             rem[u] -= 1 } else v = next[u]; o[p] = v; u = v
+ * L = 0 writes nothing; L = 1, 2 come back unchanged.  Output: the 2-bit code is 0 where the letter is 4; word and
+ * validity bits beyond a sequence's end are 0.  d_valid = NULL: every base is valid, and d_out_valid may then be NULL
+ * (not written).  The output buffers must differ from the inputs; seq0 + n_seq <= 2^32; n_seq = 0 does nothing;
+ * PENGK_ERR_ARG otherwise.  Asynchronous on the context's stream. */
+int pengk_shuffle_sequences(pengk_ctx* ctx, uint64_t seed, uint64_t seq0, uint64_t n_seq, const uint64_t* d_words,
+                            const uint32_t* d_valid, const int64_t* d_offs, const uint32_t* d_lens, uint64_t* d_out_words,
+                            uint32_t* d_out_valid);
 /* Best window score of every motif on every sequence (the ZOOPS scan of scripts/shoot_peng.py's FDR call):
  * h_S = n_motifs x PENGK_MAX_MOTIF_LEN x 4 int32 log-odds (rows beyond h_len[m] unused), 1 <= h_len[m] <=
  * PENGK_MAX_MOTIF_LEN, |S| <= 2000.  d_best[m * n_seq + i] = max over the windows of sequence i whose bases are all

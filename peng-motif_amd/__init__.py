@@ -32,6 +32,7 @@ EXPORTS = [
     "pengk_comm_host_init_env", "pengk_comm_host_info", "pengk_comm_host_allgather", "pengk_comm_host_allreduce_u64",
     "pengk_comm_host_shutdown",
     "pengk_scan_layout_words", "pengk_scan_layout_build", "pengk_synth_scan_sequences", "pengk_sample_background",
+    "pengk_shuffle_sequences",
     "pengk_motif_scan", "pengk_score_histograms", "pengk_score_summary",
     "pengk_score_tail_pvalues", "pengk_score_threshold", "pengk_sites_count", "pengk_sites_slices", "pengk_sites_emit",
     "pengk_sites_histograms", "pengk_sites_qvalues", "pengk_qvalue_threshold",
@@ -149,6 +150,7 @@ def lib():
         L.pengk_scan_layout_build.argtypes = [vp, vp, i64, u64, vp, vp, vp, vp]
         L.pengk_synth_scan_sequences.argtypes = [vp, u64, u64, u64, C.c_uint32, vp, vp, vp, vp]
         L.pengk_sample_background.argtypes = [vp, u64, u64, u64, vp, vp, C.c_int, vp, vp]
+        L.pengk_shuffle_sequences.argtypes = [vp, u64, u64, u64, vp, vp, vp, vp, vp, vp]
         L.pengk_motif_scan.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, vp, vp, C.c_int, vp]
         L.pengk_score_histograms.argtypes = [vp, C.c_int, vp, u64, vp, vp, vp, vp]
         L.pengk_score_summary.argtypes = [vp, vp, u64, C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -554,6 +556,18 @@ class Context:
         _check(lib().pengk_sample_background(self.h, seed, seq0, scan[4], _ptr(scan[2]), _ptr(scan[3]), K, th.ctypes.data,
                                              _ptr(words)))
         return words
+
+    def shuffle_sequences(self, scan, seed, seq0, all_valid=False, words=None, valid=None):
+        """dinucleotide-preserving shuffles of the sequences of `scan` in its layout (device): (words, valid).
+        all_valid: the input's validity words are not read (d_valid = NULL) and validity words are written only into a
+        `valid` buffer given by the caller (else None is returned for them)"""
+        if words is None:
+            words = self.empty(scan[0].shape, np.uint64)
+        if valid is None and not all_valid:
+            valid = self.empty(scan[1].shape, np.uint32)
+        _check(lib().pengk_shuffle_sequences(self.h, seed, seq0, scan[4], _ptr(scan[0]), None if all_valid else _ptr(scan[1]),
+                                             _ptr(scan[2]), _ptr(scan[3]), _ptr(words), None if valid is None else _ptr(valid)))
+        return words, valid
 
     def motif_scan(self, scan, S, lens, both, words=None, all_valid=False, best=None):
         """best[m, i] of every motif on every sequence of `scan`; S: n x w x 4 int32 (padded to MAX_MOTIF_LEN here)"""

@@ -3,6 +3,8 @@
 //
 //   scan layout    host builder: byte codes -> 2-bit words + validity words, every sequence from a 32-base boundary
 //   sampler        one thread per sequence, order-K Markov chain, counter-based draws: shards reproduce one process
+//   shuffle         one thread per sequence, its 25 doublet counters in LDS: a negative with the
+//                  sequence's own dinucleotide counts (shuffle_core.h)
 //   scan           motif groups whose 4-mer chunk tables fit in LDS; one thread per sequence slides a 64-base look-ahead
 //                  buffer over its words, so chunk c of the window is byte c of the buffer
 //   histograms     per-motif integer histograms of the best scores (LDS bins for the top of the range, global beyond)
@@ -17,6 +19,7 @@
 #include <vector>
 
 #include "pengk_internal.h"
+#include "shuffle_core.h"
 
 namespace pengk {
 namespace {
@@ -192,6 +195,29 @@ __global__ __launch_bounds__(256) void sample_background_kernel(uint64_t seed, u
       }
       wp[j] = v;
     }
+  }
+}
+
+// pengk_shuffle_sequences: one thread per sequence, grid-stride like the sampler.  The 25 counters of a thread are
+// indexed at run time, so they live in LDS (25 KiB per workgroup; a private array would go to scratch): counter k of
+// thread t at dword k * SHUFFLE_THREADS + t, bank t % 32 whatever k is.  No barrier: a thread touches its own only.
+constexpr int SHUFFLE_THREADS = 256;
+constexpr int SHUFFLE_BLOCKS_PER_CU = 6;  // the workgroups whose counters fit in a CU's 160 KiB of LDS
+
+__global__ __launch_bounds__(SHUFFLE_THREADS) void shuffle_sequences_kernel(uint64_t seed, uint64_t seq0, uint64_t n_seq,
+                                                                            const uint64_t* __restrict__ words,
+                                                                            const uint32_t* __restrict__ valid,
+                                                                            const int64_t* __restrict__ offs,
+                                                                            const uint32_t* __restrict__ lens,
+                                                                            uint64_t* __restrict__ out_words,
+                                                                            uint32_t* __restrict__ out_valid) {
+  __shared__ uint32_t cnt[25 * SHUFFLE_THREADS];
+  for (uint64_t i = blockIdx.x * (uint64_t)SHUFFLE_THREADS + threadIdx.x; i < n_seq; i += (uint64_t)gridDim.x * SHUFFLE_THREADS) {
+    const uint32_t L = lens[i];
+    if (L == 0) continue;
+    const uint64_t w0 = (uint64_t)offs[i] >> 5;
+    shuffle_sequence<SHUFFLE_THREADS>(seed, seq0 + i, words + w0, valid ? valid + w0 : nullptr, L, cnt + threadIdx.x,
+                                      out_words + w0, out_valid ? out_valid + w0 : nullptr);
   }
 }
 
@@ -1144,6 +1170,23 @@ int pengk_sample_background(pengk_ctx* ctx, uint64_t seed, uint64_t seq0, uint64
   memcpy(th.t, h_thresholds, (size_t)n_ctx * 3 * sizeof(uint32_t));
   hipLaunchKernelGGL(sample_background_kernel, dim3(grid_for(ctx, n_seq, 256, 16)), dim3(256), 0, ctx->stream, seed, seq0, n_seq,
                      d_offs, d_lens, K, th, d_words);
+  PENGK_HIP(hipGetLastError());
+  return PENGK_OK;
+}
+
+int pengk_shuffle_sequences(pengk_ctx* ctx, uint64_t seed, uint64_t seq0, uint64_t n_seq, const uint64_t* d_words,
+                            const uint32_t* d_valid, const int64_t* d_offs, const uint32_t* d_lens, uint64_t* d_out_words,
+                            uint32_t* d_out_valid) {
+  if (!ctx || (n_seq && (!d_words || !d_offs || !d_lens || !d_out_words || (d_valid && !d_out_valid))))
+    return fail(PENGK_ERR_ARG, "pengk_shuffle_sequences: bad argument");
+  if (n_seq && (d_out_words == d_words || (d_out_valid && d_out_valid == d_valid)))
+    return fail(PENGK_ERR_ARG, "pengk_shuffle_sequences: the output buffers must differ from the input");
+  if (seq0 + n_seq > (1ull << 32)) return fail(PENGK_ERR_ARG, "pengk_shuffle_sequences: sequence index beyond 2^32");
+  SCORE_ENTER(ctx);
+  if (n_seq == 0) return PENGK_OK;
+  hipLaunchKernelGGL(shuffle_sequences_kernel, dim3(grid_for(ctx, n_seq, SHUFFLE_THREADS, SHUFFLE_BLOCKS_PER_CU)),
+                     dim3(SHUFFLE_THREADS), 0, ctx->stream, seed, seq0, n_seq, d_words, d_valid, d_offs, d_lens, d_out_words,
+                     d_out_valid);
   PENGK_HIP(hipGetLastError());
   return PENGK_OK;
 }

@@ -44,6 +44,7 @@ unsigned Global::minimum_processed_motifs = 0;
 int Global::maximum_optimized_patterns = 50;
 bool Global::scoreMotifs = false;
 unsigned long long Global::scoreSeed = 1;
+bool Global::scoreNegativesShuffled = false;
 char* Global::sitesFilename = nullptr;
 double Global::sitesPvalue = 1e-4;
 bool Global::sitesQvalue = false;
@@ -208,6 +209,15 @@ void Global::readArguments(int nargs, char* args[]) {
       scoreMotifs = true;
     } else if (!strcmp(a, "--score-seed")) {
       scoreSeed = std::stoull(need(i, nargs, args, printHelp));
+    } else if (!strcmp(a, "--score-negatives")) {
+      const char* v = need(i, nargs, args, printHelp);
+      if (!strcmp(v, "sampled")) scoreNegativesShuffled = false;
+      else if (!strcmp(v, "shuffled")) scoreNegativesShuffled = true;
+      else {
+        printHelp();
+        log_line("ERROR", "Unknown expression following --score-negatives");
+        exit(4);
+      }
     } else if (!strcmp(a, "--sites")) {
       sitesFilename = (char*)need(i, nargs, args, printHelp);
     } else if (!strcmp(a, "--sites-pvalue")) {
@@ -336,7 +346,10 @@ void Global::printHelp() {
   printf("  --max-optimized-patterns INT       (default 50)\n");
   printf("  --score-motifs                 score every motif against as many sequences sampled from the background\n");
   printf("                                 model (zoops_score = AUC, occur) and rank the motifs by it\n");
-  printf("  --score-seed INT               seed of the sampled sequences (default 1)\n");
+  printf("  --score-seed INT               seed of the sampled or shuffled sequences (default 1)\n");
+  printf("  --score-negatives STRING       sampled: the negatives of --score-motifs come from the background model;\n");
+  printf("                                 shuffled: every input sequence shuffled with its own dinucleotide counts\n");
+  printf("                                 kept, for inputs of mixed composition (default sampled)\n");
   printf("  --sites FILE                   write every occurrence of the motifs (TSV: sequence, position, strand,\n");
   printf("                                 score, p-value) at p-value --sites-pvalue or below\n");
   printf("  --sites-pvalue FLOAT           p-value threshold of --sites, in (0, 1] (default 1e-4)\n");

@@ -59,6 +59,7 @@ class Global {
 
   static bool scoreMotifs;                   // --score-motifs (new: scripts/shoot_peng.py's scoring step, on the device)
   static unsigned long long scoreSeed;       // --score-seed
+  static bool scoreNegativesShuffled;        // --score-negatives shuffled (new: every sequence's own dinucleotide-preserving shuffle)
   static char* sitesFilename;                // --sites (new: every motif occurrence with its p-value)
   static double sitesPvalue;                 // --sites-pvalue
   static bool sitesQvalue;                   // --sites-qvalue (new: a q-value column in the sites file)

@@ -116,7 +116,7 @@ int main(int nargs, char** args) {
     // the writers' order first, then stable by zoops_score descending (scripts/shoot_peng.py re-ranks the motifs so)
     std::sort(result.begin(), result.end(), sort_IUPAC_patterns);
     scores = score_motifs(result, *Global::inputSequenceSet, *scan, *bgModel, Global::bgModelOrder,
-                          Global::strand == Strand::BOTH_STRANDS, Global::scoreSeed);
+                          Global::strand == Strand::BOTH_STRANDS, Global::scoreSeed, Global::scoreNegativesShuffled);
     std::vector<size_t> order(result.size());
     for (size_t i = 0; i < order.size(); ++i) order[i] = i;
     std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return scores[a].zoops_score > scores[b].zoops_score; });

@@ -86,7 +86,7 @@ void build_scan_input(SequenceSet& set, ScanInput* in) {
 }
 
 std::vector<MotifScore> score_motifs(const std::vector<IUPACPattern*>& pats, SequenceSet& set, const ScanInput& in,
-                                     BackgroundModel& bg, int K, bool both_strands, uint64_t seed) {
+                                     BackgroundModel& bg, int K, bool both_strands, uint64_t seed, bool shuffled) {
   using pengk_host::check;
   using pengk_host::DeviceBuffer;
   pengk_host::Lap lap("  score: ");
@@ -95,6 +95,13 @@ std::vector<MotifScore> score_motifs(const std::vector<IUPACPattern*>& pats, Seq
   const size_t n_local = in.n_local;
   const uint64_t n_words = in.n_words;
   DeviceBuffer<uint64_t> d_neg(n_words);
+  DeviceBuffer<uint32_t> d_neg_valid;  // (a shuffle carries the sequence's other letters along)
+  if (shuffled) {
+    d_neg_valid.resize(n_words);
+    // (the sampled path stays silent, as it was)
+    if (pengk_host::rank() == 0)
+      std::cerr << "score: negatives are dinucleotide-preserving shuffles of the input sequences (seed " << seed << ")" << std::endl;
+  }
 
   // log-odds against the background letter frequencies, score ranges, histogram offsets
   const float* bg0 = bg.getV()[0];
@@ -132,16 +139,21 @@ std::vector<MotifScore> score_motifs(const std::vector<IUPACPattern*>& pats, Seq
         "pengk_motif_scan");
   check(pengk_score_histograms(ctx, n_motifs, d_best.get(), n_local, lo.data(), hi.data(), hoffs.data(), d_hist.get()),
         "pengk_score_histograms");
-  check(pengk_sample_background(ctx, seed, set.getLocalBase(), n_local, in.d_offs.get(), in.d_lens.get(), K, thr.data(), d_neg.get()),
-        "pengk_sample_background");
-  check(pengk_motif_scan(ctx, d_neg.get(), nullptr, in.d_offs.get(), in.d_lens.get(), n_local, n_motifs, S.data(), len.data(), both,
-                         d_best.get()),
+  if (shuffled)
+    check(pengk_shuffle_sequences(ctx, seed, set.getLocalBase(), n_local, in.d_words.get(), in.d_valid.get(), in.d_offs.get(),
+                                  in.d_lens.get(), d_neg.get(), d_neg_valid.get()),
+          "pengk_shuffle_sequences");
+  else
+    check(pengk_sample_background(ctx, seed, set.getLocalBase(), n_local, in.d_offs.get(), in.d_lens.get(), K, thr.data(), d_neg.get()),
+          "pengk_sample_background");
+  check(pengk_motif_scan(ctx, d_neg.get(), shuffled ? d_neg_valid.get() : nullptr, in.d_offs.get(), in.d_lens.get(), n_local, n_motifs,
+                         S.data(), len.data(), both, d_best.get()),
         "pengk_motif_scan");
   check(pengk_score_histograms(ctx, n_motifs, d_best.get(), n_local, lo.data(), hi.data(), hoffs.data(), d_hist.get() + nh),
         "pengk_score_histograms");
   std::vector<long long> hist(2 * nh);
   d_hist.download((uint64_t*)hist.data(), 2 * nh);
-  lap("sample + scan + histograms");
+  lap(shuffled ? "shuffle + scan + histograms" : "sample + scan + histograms");
   SequenceSet::allreduceSum(hist.data(), hist.size());  // (integers: the ranks' sum is exact)
   for (int m = 0; m < n_motifs; ++m)
     check(pengk_score_summary((const uint64_t*)hist.data() + hoffs[m], (const uint64_t*)hist.data() + nh + hoffs[m],

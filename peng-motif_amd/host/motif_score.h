@@ -34,14 +34,16 @@ void motif_log_odds(const std::vector<IUPACPattern*>& pats, const float* bg0, st
                     const char* who);
 
 struct MotifScore {
-  double zoops_score = 0.0;  // AUC of the best window scores, input against sampled sequences
+  double zoops_score = 0.0;  // AUC of the best window scores, input against its negatives (sampled or shuffled)
   double occur = 0.0;        // share of input sequences with a site, estimated at 1 % false positives
 };
 
 // Scores pats (in their order) over this rank's records of `set` and the negatives of their global indices; the
 // histograms are summed over the ranks, so every rank gets the scores of the whole input.  K: the order of the
-// sampling model (--bg-model-order), V from bg.  Collective in a multi-rank run.
+// sampling model (--bg-model-order), V from bg.  shuffled (--score-negatives shuffled): the negative of a sequence is
+// its own dinucleotide-preserving shuffle (pengk_shuffle_sequences: same seed, same global indices) with validity bits
+// of its own, not a sample of the model.  Collective in a multi-rank run.
 std::vector<MotifScore> score_motifs(const std::vector<IUPACPattern*>& pats, SequenceSet& set, const ScanInput& in,
-                                     BackgroundModel& bg, int K, bool both_strands, uint64_t seed);
+                                     BackgroundModel& bg, int K, bool both_strands, uint64_t seed, bool shuffled = false);
 
 #endif

@@ -1,7 +1,9 @@
 """Times the motif scoring on the device (include/pengk.h, "motif scoring") for N motifs over the device-generated
 configs[2] input (pengk_synth_scan_sequences: 10M x 200 bp) plus as many sampled negatives: sampling, the two scans and
 the two histogram passes, each between device events (median of --reps after one warm-up).  Prints one JSON line.
-  python tools/score_probe.py [--n-seq 10000000] [--L 200] [--motifs 16] [--reps 5] [--plus]"""
+--negatives shuffled: the negatives are the input's dinucleotide-preserving shuffles (pengk_shuffle_sequences, DESIGN.md
+16) and are scanned with their own validity words; the first time is then the shuffle kernel's alone.
+  python tools/score_probe.py [--n-seq 10000000] [--L 200] [--motifs 16] [--reps 5] [--plus] [--negatives sampled|shuffled]"""
 import argparse
 import json
 import os
@@ -20,6 +22,7 @@ def main():
     ap.add_argument("--motifs", type=int, default=16)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--plus", action="store_true")
+    ap.add_argument("--negatives", choices=["sampled", "shuffled"], default="sampled")
     a = ap.parse_args()
     ctx = pk.Context(0)
     n, L = a.n_seq, a.L
@@ -33,6 +36,9 @@ def main():
     th = np.array([min(int(np.floor(c * 2.0 ** 32)), 2 ** 32 - 1) for k in range(3) for row in V[k] for c in np.cumsum(row)[:3]],
                   np.uint32)
     neg = ctx.empty(scan[0].shape, np.uint64)
+    shuffled = a.negatives == "shuffled"
+    neg_valid = ctx.empty(scan[1].shape, np.uint32) if shuffled else None
+    neg_scan = (neg, neg_valid, scan[2], scan[3], n)
     best = ctx.empty((len(widths), n), np.int32)
     both = not a.plus
     ev = [ctx.timer() for _ in range(6)]
@@ -40,13 +46,19 @@ def main():
     for rep in range(a.reps + 1):
         hist = None
         ctx.record(ev[0])
-        ctx.sample_background(scan, 1, 0, 2, th, words=neg)
+        if shuffled:
+            ctx.shuffle_sequences(scan, 1, 0, words=neg, valid=neg_valid)
+        else:
+            ctx.sample_background(scan, 1, 0, 2, th, words=neg)
         ctx.record(ev[1])
         ctx.motif_scan(scan, S, widths, both, best=best)
         ctx.record(ev[2])
         hist, _ = ctx.score_histograms(best, n, lo, hi)
         ctx.record(ev[3])
-        ctx.motif_scan(scan, S, widths, both, words=neg, all_valid=True, best=best)
+        if shuffled:
+            ctx.motif_scan(neg_scan, S, widths, both, best=best)
+        else:
+            ctx.motif_scan(scan, S, widths, both, words=neg, all_valid=True, best=best)
         ctx.record(ev[4])
         ctx.score_histograms(best, n, lo, hi, hist=hist)
         ctx.record(ev[5])
@@ -60,7 +72,8 @@ def main():
     windows = sum(2 * n * (L - w + 1) for w in widths)  # (both sets; per strand)
     total = float(t.sum())
     print(json.dumps({"probe": "motif_score", "n_seq": n, "L": L, "motifs": len(widths), "widths": widths,
-                      "strands": 2 if both else 1, "sample_ms": round(t[0], 3), "scan_pos_ms": round(t[1], 3),
+                      "strands": 2 if both else 1, "negatives": a.negatives,
+                      "shuffle_ms" if shuffled else "sample_ms": round(t[0], 3), "scan_pos_ms": round(t[1], 3),
                       "hist_pos_ms": round(t[2], 3), "scan_neg_ms": round(t[3], 3), "hist_neg_ms": round(t[4], 3),
                       "total_ms": round(total, 3), "window_scores_per_s": windows * (2 if both else 1) / (total * 1e-3),
                       "reps": a.reps}))
