@@ -3,7 +3,9 @@
 // repository, never shipped to the GPU box).
 //
 // TEST INFRASTRUCTURE ONLY.  It exists to (a) pin oracle/peng_oracle.cpp and (b) produce the
-// golden vectors committed under tests/golden/ (see tests/golden/make_golden.py).
+// golden vectors committed under tests/golden/ (see tests/golden/make_golden.py).  The edge fixtures tests/golden/edges_*.npz
+// come from its sibling oracle/ref_edges.cpp (constructed tables injected into the same classes) and, for the count cases,
+// from this program's `tables` mode; tests/golden/make_edge_golden.py regenerates them.
 //
 // usage: ref_dump <fasta> <W> <BOTH|PLUS> <outdir> [tables]
 // writes raw little-endian arrays + text tables into <outdir>.

@@ -600,6 +600,11 @@ CLASSES = dict(item_lengths=item_lengths, alignment=alignment, periods=periods, 
                long_fixup=long_fixup, runs_and_N=runs_and_N)
 
 
+def case_tag(cls, part, W, both):
+    """the unique name of a part under a strand mode (the key of its entry in tests/golden/edges_count_w*.npz)"""
+    return "%s/%s/W%d/%s" % (cls, part["name"], W, "both" if both else "plus")
+
+
 @functools.lru_cache(None)
 def packed(cls, W):
     """the parts of a class as the host packer packs them"""

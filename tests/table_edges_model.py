@@ -203,6 +203,12 @@ def sweep_cases(W, both):
     return small_sweep_cases(W, both) if W <= 10 else big_sweep_cases(W, both)
 
 
+def sweep_tag(W, both, case):
+    """the unique name of a sweep case (the key of its entry in tests/golden/edges_tables_w*.npz)"""
+    v, lt, k, mk, mir = case
+    return "sweep/W%d/%s/V%s/ltot%d/k%d/maxk%d/%s" % (W, "both" if both else "plus", v, lt, k, mk, "mirrored" if mir else "as_built")
+
+
 _bgp = {"key": None, "orders": {}}
 
 

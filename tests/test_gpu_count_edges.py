@@ -4,11 +4,17 @@ lengths up to the 16-bit window field, every stream alignment, repeats of every 
 either side of a prologue, fix-ups that walk back to the head of a long run, runs cut by invalid bases.  Everything is
 integer and compared bit for bit: with the oracle at W <= 12, with the model's sparse reference at W = 14, and the
 number of deferred items with the model's prediction.  tests/test_count_edges_cpu.py asserts that the inputs hold the
-classes they are built for.  (Stream offsets above 2^32 bases need a large input: tests/test_gpu_fullsize.py.)"""
+classes they are built for.  (Stream offsets above 2^32 bases need a large input: tests/test_gpu_fullsize.py.)
+
+And directly against the COMPILED REFERENCE at W <= 12 (tests/golden/edges_count_w*.npz, written by
+tests/golden/make_edge_golden.py from the reference's own count of the same sequences): the sha256 of the device's table,
+the stored bins and ltot, for every emitter.  W = 14 stays oracle-only: the reference's size_t counter table alone is
+2 GiB there.  These tests read tests/golden only, never the reference."""
 import numpy as np
 import pytest
 
 import count_edges_model as cm
+import edge_fixtures as ef
 import peng_motif_amd as pk
 from oracle import oracle as po
 
@@ -98,6 +104,29 @@ def first_difference(got, want):
     return "%d bins differ, the first: bin %d, device %d, reference %d" % (bad.size, bad[0], got[bad[0]], want[bad[0]])
 
 
+_SEEN = {}  # (class, W): {(tag, emitter): (sha256 of the device's table, its stored bins, ltot, fused background counters)}
+
+
+def _against_the_reference(cls, part, W, both, impl, got, lt, bg):
+    """what the reference test needs of a device table, taken while the oracle test has it in hand"""
+    fix = ef.load(ef.count_file(W))
+    tag = ef.count_tag(cls, part, W, both)
+    r = fix["index"].get(tag)
+    idx = fix["slice_idx"][fix["slice_off"][r]:fix["slice_off"][r + 1]].astype(np.int64) if r is not None else np.zeros(0, np.int64)
+    _SEEN.setdefault((cls, W), {})[tag, impl] = (ef.digest(got), got[idx], lt, bg)
+
+
+def _count_class(ctx, cls, W):
+    """every part of a class under both strand modes and every emitter, noted in _SEEN"""
+    for part, p in zip(cm.CLASSES[cls](W), cm.packed(cls, W)):
+        for both in (False, True):
+            for impl in emitters(W):
+                ctx.upload(p)
+                counts, lt, bg, deferred = run(ctx, both, impl, p.all_whole)
+                got = counts.to_host().astype(np.uint64)
+                _against_the_reference(cls, part, W, both, impl, got, lt, bg)
+
+
 @pytest.mark.parametrize("W", cm.WS)
 @pytest.mark.parametrize("cls", CLS)
 def test_classes_against_the_oracle(ctx, cls, W):
@@ -113,12 +142,43 @@ def test_classes_against_the_oracle(ctx, cls, W):
                 ctx.upload(p)
                 counts, lt, bg, deferred = run(ctx, both, impl, p.all_whole)
                 got = counts.to_host().astype(np.uint64)
+                _against_the_reference(cls, part, W, both, impl, got, lt, bg)
                 assert np.array_equal(got, want), "%s: %s" % (what, first_difference(got, want))
                 assert lt == ltot, what
                 assert deferred == defer_want, "%s: %d items deferred, the model says %d" % (what, deferred, defer_want)
                 if p.all_whole:
                     assert np.array_equal(bg, bg_want), what
                     assert np.array_equal(ctx.bg_count().to_host().astype(np.int64), bg_want), what
+
+
+@pytest.mark.parametrize("W", cm.WS)
+@pytest.mark.parametrize("cls", CLS)
+def test_classes_against_the_reference(ctx, cls, W):
+    """The device's tables of test_classes_against_the_oracle (counted again only if that test did not run) against the
+    compiled reference's fixture: inputs first (sha256 of codes and offsets: "inputs drifted" means regenerate), then the
+    sha256 of the mirrored table, the stored bins (every count value the table holds, the largest bins, zero bins next
+    to them; the whole table for W <= 6), ltot and the fused background counters -- for every emitter."""
+    tags = [ef.count_tag(cls, part, W, both) for part in cm.CLASSES[cls](W) for both in (False, True)]
+    if not all((t, impl) in _SEEN.get((cls, W), {}) for t in tags for impl in emitters(W)):
+        _count_class(ctx, cls, W)
+    fix = ef.load(ef.count_file(W))
+    seen = _SEEN[cls, W]
+    for part, p in zip(cm.CLASSES[cls](W), cm.packed(cls, W)):
+        for both in (False, True):
+            tag = ef.count_tag(cls, part, W, both)
+            drift = ef.inputs_match(fix, tag, ef.count_inputs(part))
+            assert drift is None, drift
+            r = fix["index"][tag]
+            a, e = fix["slice_off"][r], fix["slice_off"][r + 1]
+            for impl in emitters(W):
+                what = "%s, %s" % (tag, mode(both, impl))
+                sha, bins, lt, bg = seen[tag, impl]
+                bad = np.flatnonzero(bins != fix["slice_val"][a:e])
+                assert not bad.size, "%s: bin %d: device %d, reference %d" % (what, fix["slice_idx"][a + bad[0]], bins[bad[0]], fix["slice_val"][a + bad[0]]) if bad.size else None
+                assert np.array_equal(sha, fix["sha_counts"][r]), "%s: the table's sha256 is not the reference's (the stored bins agree)" % what
+                assert lt == int(fix["ltot"][r]), what
+                if bg is not None:
+                    assert np.array_equal(bg, fix["bgcounts"][r]), what
 
 
 def test_w14_against_the_sparse_reference(ctx, big):

@@ -6,12 +6,20 @@ count runs.  tests/test_table_edges_cpu.py asserts that the cases hold the class
 Bars, the project's own (tests/test_gpu_parity.py): V, bgprob[0..max_k], expected, z and the IUPAC sums bit for bit; log-p
 within 1 float ulp (device log against glibc's); infinities agree exactly; NaN agrees in position (x86 and gfx950
 produce different NaN signs for 0/0, so not in bits); the similarity grid within 5e-4 of the reference's float32 running
-sums, -inf exactly where they give -inf."""
+sums, -inf exactly where they give -inf.
+
+And directly against the COMPILED REFERENCE at W <= 12 (tests/golden/edges_tables_*.npz, written by
+tests/golden/make_edge_golden.py from the reference's own classes with these tables injected): V bit for bit; of every
+sweep table the sha256 (NaN in canonical form, for the reason above) and the stored slices; log-p at the stored slices
+within 1 ulp and without a hash (its bits are glibc's on the reference's side); the IUPAC sums bit for bit; the
+similarity grid within the same 5e-4 of the compiled calculate_S.  W = 14 stays oracle-only: the reference's size_t
+counter table alone is 2 GiB there.  These tests read tests/golden only, never the reference."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import edge_fixtures as ef
 import peng_motif_amd as pk
 import table_edges_model as tm
 from oracle import oracle as po
@@ -75,6 +83,31 @@ def test_background_model_on_constructed_counters(ctx):
 
 
 # ---- sweep -----------------------------------------------------------------------------------------------------------
+_SWEEPS = {}  # (tag, kernel): {"idx": the fixture's slice indices, table: (sha256 of the device's table, its values at idx)}
+
+
+def _note_sweep(c, kernel):
+    """what the reference test needs of the device's tables of a case, taken while the oracle test has them in hand"""
+    seen = {"idx": np.zeros(0, np.int64)}
+    if c["W"] in ef.TABLE_WS:
+        seen["sha_in"] = [ef.digest(a) for a in ef.sweep_inputs(c)]
+        fix = ef.load(ef.table_file(c["W"]))
+        tag = ef.sweep_tag(c["W"], c["both"], (c["vkind"], c["ltot"], c["k"], c["max_k"], c["mirrored"]))
+        if tag in fix["index"]:
+            idx = fix["slice_idx"][fix["index"][tag]].astype(np.int64)
+            seen["idx"] = idx[idx >= 0]
+        _SWEEPS[tag, kernel] = seen
+    return seen
+
+
+def _note_table(seen, name, got):
+    seen[name] = (None if name == "logp" else ef.table_digest(got), got[seen["idx"]].copy())
+
+
+def _sweep_kernels(W, both):
+    return ("twin-tile", "per-pattern") if (W >= 12 and both) else ("per-pattern",)
+
+
 def _run_sweep_case(ctx, c, d_V, failures):
     W, both = c["W"], c["both"]
     d_lt = pk.DeviceArray.from_host(ctx, np.array([c["ltot"]], np.uint64))
@@ -84,7 +117,9 @@ def _run_sweep_case(ctx, c, d_V, failures):
         ctx.set_option("sweep_pairs", pairs)
         out = ctx.pattern_stats(W, both, c["k"], c["max_k"], d_V, d_lt, d_c)
         bgp = out[0].to_host()
+        seen = _note_sweep(c, kernel)
         for o in range(c["max_k"] + 1):
+            _note_table(seen, "bgp%d" % o, bgp[o])
             bad = _mismatch(bgp[o], c["bgp"][o])
             if bad.size:
                 failures.append(_describe(c, "bgprob[%d]" % o, bad[0], bgp[o], c["bgp"][o], kernel) + " (%d patterns)" % bad.size)
@@ -92,6 +127,7 @@ def _run_sweep_case(ctx, c, d_V, failures):
         for what, d, want, cmp in (("expected", out[1], c["expected"], _mismatch), ("z", out[3], c["z"], _mismatch),
                                    ("log-p", out[2], c["logp"], _beyond_one_ulp)):
             got = d.to_host()
+            _note_table(seen, {"expected": "expected", "z": "z", "log-p": "logp"}[what], got)
             bad = cmp(got, want)
             if bad.size:
                 failures.append(_describe(c, what, bad[0], got, want, kernel) + " (%d patterns)" % bad.size)
@@ -124,6 +160,76 @@ def test_sweep_on_edge_tables(ctx, W, both):
     finally:
         ctx.set_option("sweep_pairs", 1)
     assert not failures, "%d mismatches, the first ones:\n%s" % (len(failures), "\n".join(failures[:8]))
+
+
+@pytest.mark.parametrize("both", [False, True])
+@pytest.mark.parametrize("W", ef.TABLE_WS)
+def test_sweep_on_edge_tables_against_the_reference(ctx, W, both):
+    """The device's tables of test_sweep_on_edge_tables (computed again only if that test did not run) against the
+    compiled reference's fixture, for every case and kernel: inputs first ("inputs drifted" means regenerate); then
+    bgprob[0..max_k], expected and z by sha256 and at the stored slices (zero-count bins, the mu edges and every other
+    count edge, palindromes, own-twin tiles, seeds) bit for bit, NaN in position; log-p at the stored slices within 1
+    ulp."""
+    fix = ef.load(ef.table_file(W))
+    cases = tm.sweep_cases(W, both)
+    tags = [ef.sweep_tag(W, both, case) for case in cases]
+    rerun = not all((t, k) in _SWEEPS and len(_SWEEPS[t, k]) > 2 for t in tags for k in _sweep_kernels(W, both))
+    failures = []
+    d_V = {}
+    try:
+        for case, tag in zip(cases, tags):
+            if rerun:
+                c = tm.sweep_case(W, both, case)
+                if case[0] not in d_V:
+                    d_V[case[0]] = pk.DeviceArray.from_host(ctx, c["V"])
+                _run_sweep_case(ctx, c, d_V[case[0]], [])
+                del c
+            assert tag in fix["index"], "case %s has no fixture entry: regenerate with tests/golden/make_edge_golden.py" % tag
+            r = fix["index"][tag]
+            for kernel in _sweep_kernels(W, both):
+                seen = _SWEEPS[tag, kernel]
+                for j, d in enumerate(seen["sha_in"]):
+                    assert np.array_equal(d, fix["sha_in"][r, j]), "inputs drifted: input %d of case %s; regenerate" % (j, tag)
+                n = seen["idx"].size
+                for j, name in enumerate(ef.SWEEP_TABLES):
+                    if name not in seen:  # (an order beyond max_k)
+                        assert not fix["sha_out"][r, j].any(), (tag, name)
+                        continue
+                    sha, vals = seen[name]
+                    want = fix["slice_val"][r, j, :n].view(np.float32)
+                    bad = _beyond_one_ulp(vals, want) if name == "logp" else _mismatch(vals, want)
+                    if bad.size:
+                        x = int(seen["idx"][bad[0]])
+                        failures.append("%s, kernel %s: %s, pattern %d (%s): device %r (0x%08x), reference %r (0x%08x)"
+                                        % (tag, kernel, name, x, po.kmer_str(x, W), float(vals[bad[0]]), int(vals[bad[0]:bad[0] + 1].view(np.uint32)[0]),
+                                           float(want[bad[0]]), int(want[bad[0]:bad[0] + 1].view(np.uint32)[0])))
+                    elif sha is not None and not np.array_equal(sha, fix["sha_out"][r, j]):
+                        failures.append("%s, kernel %s: %s: the table's sha256 is not the reference's (the stored slice agrees)" % (tag, kernel, name))
+    finally:
+        ctx.set_option("sweep_pairs", 1)
+    assert not failures, "%d mismatches, the first ones:\n%s" % (len(failures), "\n".join(failures[:8]))
+
+
+def test_background_model_against_the_reference(ctx):
+    """pengk_bg_model on the constructed counters that fit the reference's `int` (every kind but above_2_31, every alpha
+    and order) against the V the compiled calculateV() made of them: bit for bit."""
+    fix = ef.load(ef.MISC_FILE)
+    rows = [t for t, cl in zip(fix["tags"], fix["classes"]) if cl == "bg"]
+    done = 0
+    for (name, n, K, alpha, _), (tag, used, _, _, in_range) in zip(tm.bg_model_cases(), ef.bg_cases()):
+        assert tag == "bg/" + name
+        if not in_range:
+            continue
+        drift = ef.inputs_match(fix, tag, ef.bg_inputs(used, K, alpha))
+        assert drift is None, drift
+        d_n = pk.DeviceArray.from_host(ctx, n.astype(np.uint64))
+        d_V = pk.DeviceArray.from_host(ctx, np.full(84, np.float32(-7.0)))
+        got = ctx.bg_model(d_n, K, alpha, out=d_V).to_host()
+        want = fix["bg_V"][rows.index(tag)]
+        bad = np.flatnonzero(got.view(np.uint32) != want)
+        assert not bad.size, "V differs: %s, entry %d: device %r, reference %r" % (name, bad[0], got[bad[0]], want[bad[0]:bad[0] + 1].view(np.float32)[0]) if bad.size else None
+        done += 1
+    assert done == len(rows)
 
 
 # ---- seed candidates ---------------------------------------------------------------------------------------------------
@@ -175,6 +281,10 @@ def test_seed_candidates_on_constructed_z(ctx, W):
 
 
 # ---- IUPAC aggregation -------------------------------------------------------------------------------------------------
+_IUPAC = {}  # (W, both, V, budget): (the device's columns, the ids' names, sha256 of the inputs)
+_IUPAC_FIELDS = ("sites", "bg_p", "expected", "zscore", "log_pvalue")
+
+
 @pytest.mark.parametrize("vkind", ["a", "c"])
 @pytest.mark.parametrize("both", [False, True])
 @pytest.mark.parametrize("W", [10, 12])
@@ -192,6 +302,8 @@ def test_iupac_aggregation_on_edge_tables(ctx, W, both, vkind):
         for budget in (0, (8 << 20) if W == 10 else (64 << 20)):
             ctx.set_option("iupac_group_bytes", budget)
             out = ctx.iupac_aggregate(W, both, c["ids"], d_counts, d_bgp, d_exp)
+            _IUPAC[W, both, vkind, budget] = ({f: np.array(out[f], copy=True) for f in _IUPAC_FIELDS}, list(c["names"]),
+                                              [ef.digest(a) for a in ef.iupac_inputs(c)])
             for j, w in enumerate(c["want"]):
                 where = (W, both, vkind, budget, c["names"][j], po.iupac_str(int(c["ids"][j]), W))
                 assert int(out["sites"][j]) == w.sites, where
@@ -201,6 +313,36 @@ def test_iupac_aggregation_on_edge_tables(ctx, W, both, vkind):
                     assert a == b, where + (f, float(out[f][j]), float(getattr(w, f)))
     finally:
         ctx.set_option("iupac_group_bytes", 0)
+
+
+@pytest.mark.parametrize("vkind", ["a", "c"])
+@pytest.mark.parametrize("both", [False, True])
+@pytest.mark.parametrize("W", [10, 12])
+def test_iupac_aggregation_against_the_reference(ctx, W, both, vkind):
+    """What the device returned in test_iupac_aggregation_on_edge_tables (run again only if that test did not) against
+    the compiled reference's aggregate_attributes_from_basepatterns on the same injected tables: `sites` equal, bg_p,
+    expected, z and log-p bit for bit, under both scratch budgets.  An id on which the reference's own assert aborts
+    (tests/golden/make_edge_golden.py, UNDEFINED) has no reference row and is left to the oracle test."""
+    budgets = (0, (8 << 20) if W == 10 else (64 << 20))
+    if not all((W, both, vkind, b) in _IUPAC for b in budgets):
+        test_iupac_aggregation_on_edge_tables(ctx, W, both, vkind)
+    fix = ef.load(ef.MISC_FILE)
+    tag = ef.iupac_tag(W, both, vkind)
+    k = [t for t, cl in zip(fix["tags"], fix["classes"]) if cl == "iupac"].index(tag)
+    a, e = int(fix["iupac_off"][k]), int(fix["iupac_off"][k + 1])
+    for budget in budgets:
+        out, names, shas = _IUPAC[W, both, vkind, budget]
+        for j, d in enumerate(shas):
+            assert np.array_equal(d, fix["sha_in"][fix["index"][tag], j]), "inputs drifted: input %d of case %s; regenerate" % (j, tag)
+        assert fix["iupac_names"][a:e].tolist() == names
+        for j, name in enumerate(names):
+            if fix["iupac_died"][a + j]:
+                continue
+            where = (tag, budget, name)
+            assert int(out["sites"][j]) == int(fix["iupac_sites"][a + j]), where
+            got = np.array([out[f][j] for f in _IUPAC_FIELDS[1:]], np.float32).view(np.uint32)
+            want = fix["iupac_stats"][4 * (a + j):4 * (a + j) + 4]
+            assert np.array_equal(got, want), where + (got.view(np.float32).tolist(), want.view(np.float32).tolist())
 
 
 # ---- similarity grid ---------------------------------------------------------------------------------------------------
@@ -243,3 +385,23 @@ def test_similarity_grid_from_1_to_64_columns(ctx, both):
         col = np.full(4, np.float32(-77.0))
         _similarity(ctx, pw[:nn], cp[:nn], lens[:nn], sites[:nn], both, first_new, col)
         assert (col == np.float32(-77.0)).all(), (nn, first_new)
+
+
+@pytest.mark.parametrize("both", [False, True])
+def test_similarity_grid_against_the_compiled_reference(ctx, both):
+    """The same grid against IUPACPattern::calculate_S as the reference's compiler built it (the fixture), not its
+    restatement: within the same 5e-4 (the values agree "to ~1e-4, NOT bit for bit", include/pengk.h), -inf exactly
+    where the reference gives -inf."""
+    fix = ef.load(ef.MISC_FILE)
+    drift = ef.inputs_match(fix, ef.sim_tag(both), ef.sim_inputs())
+    assert drift is None, drift
+    want = fix["sim_S"][int(both)].view(np.float32)
+    pw, cp, lens, sites = tm.motif_set()
+    pairs = tm.pair_list(len(lens))
+    got = np.full(len(pairs), np.float32(-77.0))
+    _similarity(ctx, pw, cp, lens, sites, both, 0, got)
+    for q, (i, j) in enumerate(pairs):
+        if np.isneginf(want[q]) or np.isneginf(got[q]):
+            assert np.isneginf(want[q]) and np.isneginf(got[q]), (i, j, float(got[q]), float(want[q]))
+        else:
+            assert abs(float(got[q]) - float(want[q])) <= 5e-4, (i, j, int(lens[i]), int(lens[j]), float(got[q]), float(want[q]))

@@ -98,7 +98,10 @@ def test_iupac_aggregation(golden_dir, name):
 @pytest.mark.parametrize("name", CASES)
 def test_em(golden_dir, name):
     """mode 0 (serial float32) reproduces the reference bit for bit; mode 1 (fp64 accumulators)
-    stays inside the envelope SURVEY.md A.7 measured for the reference's own rounding error."""
+    stays inside the envelope SURVEY.md A.7 measured for the reference's own rounding error.
+    The golden files' `em_iters` are the ORACLE's iteration counts (tests/golden/make_golden.py: the reference never reports
+    its count), so `it == em_iters` pins nothing on the reference's side; the stopping rule's reference-side pin is
+    tests/test_edges_reference_cpu.py::test_em_iteration_counts, on PWMs the reference returned at every iteration cap."""
     r = pipeline(golden_dir, name)
     g = r["g"]
     for i in range(len(g["pwm_ids"])):
