@@ -71,12 +71,21 @@ void* pengk_stream(pengk_ctx* ctx);
 int pengk_set_stream(pengk_ctx* ctx, void* hip_stream);
 
 /* Tunables / introspection.  Options: "count_impl" 0 = auto, 1 = direct global atomics, 2 = partitioned LDS
- * histograms (W = 8 .. 14); "n_windows_hint" = total windows of the attached items (sizes the key buffer
+ * histograms (W = 8 .. 14); "count_group" keys per group of the partitioned scan's emitter: 0 = auto (128 -- sixteen
+ * buckets of 16-bit keys -- at W = 10 on both strands, 64 everywhere else), 64 = the emitter of 64 everywhere, 128 = as
+ * auto where it applies; a count that cannot run it (one strand, another W, the direct emitter) fails with
+ * PENGK_ERR_UNSUPPORTED (same bits either way: for A/B timing in one process and for the tests); "n_windows_hint" = total windows of the attached items (sizes the key buffer
  * tightly; set it after pengk_set_sequences); "key_cap_override" (test hook) entries per bucket region of the
  * partitioned count, 0 = automatic; "sweep_pairs" 1 (default) / 0: both strands from W = 12 on, a pattern and its reverse complement evaluated once (0: one thread per pattern; same bits); "iupac_group_bytes" (test hook) scratch budget for one group of large
  * patterns in pengk_iupac_aggregate, 0 = 1 GiB; "em_fast" 2 (default) / 1 / 0, see pengk_em; "sites_record_budget" records per slice of pengk_sites_slices
  * (default 2^24, also readable through pengk_get_info).  Info: "deferred_items" (of the last pengk_count;
- * synchronises), "num_cu"; of the last pengk_em / pengk_em_device call in the serial mode with its blocks evaluated ahead
+ * synchronises), "count_group" (the option as set), "count_group_used" (keys per group of the emitter the last count ran:
+ * 64 or 128; 0 = not the one-level partition of W = 8 / 10), "count_wrapped_workgroups" (pass-B workgroups of the last
+ * count whose packed 16-bit bins wrapped and that recounted their slices exactly; 0 under groups of 64; synchronises; like
+ * "deferred_items" it reads the count's scratch and is valid until the next pengk_count / pengk_count_bg on the context),
+ * test hooks of the same lifetime: "count_slices" (number of (wave, bucket) key slices of the last one-level count) and
+ * "count_slice_fill" (entries pass A published for the slice chosen with the option "count_probe_slice" = wave * buckets
+ * + bucket; synchronises), "num_cu"; of the last pengk_em / pengk_em_device call in the serial mode with its blocks evaluated ahead
  * (synchronise): "em_fetched_blocks" (blocks a chain added term by term), "em_mispredicted_blocks" (of those: blocks
  * whose estimated binade did not hold), "em_restaged_blocks" / "em_restaged_waits" (csrc/seqsum.h, WalkCounts). */
 int pengk_set_option(pengk_ctx* ctx, const char* name, int64_t value);

@@ -171,6 +171,16 @@ int pengk_set_option(pengk_ctx* ctx, const char* name, int64_t value) {
     ctx->count_impl = (int)value;
     return PENGK_OK;
   }
+  if (strcmp(name, "count_group") == 0) {  // (128 where it cannot run is refused by the count itself: strands and W are known there)
+    if (value != 0 && value != 64 && value != 128) return fail(PENGK_ERR_ARG, "count_group must be 0 (auto), 64 or 128 keys per group");
+    ctx->count_group = (int)value;
+    return PENGK_OK;
+  }
+  if (strcmp(name, "count_probe_slice") == 0) {
+    if (value < 0) return fail(PENGK_ERR_ARG, "count_probe_slice must be >= 0 (wave * buckets + bucket)");
+    ctx->count_probe_slice = (uint64_t)value;
+    return PENGK_OK;
+  }
   if (strcmp(name, "key_cap_override") == 0) {
     ctx->key_cap_override = (uint64_t)value;
     return PENGK_OK;
@@ -249,6 +259,36 @@ int pengk_get_info(pengk_ctx* ctx, const char* name, int64_t* value) {
       PENGK_HIP(hipMemcpyAsync(&n, ctx->d_defer_count, sizeof n, hipMemcpyDeviceToHost, ctx->stream));
       PENGK_HIP(hipStreamSynchronize(ctx->stream));
     }
+    *value = n;
+    return PENGK_OK;
+  }
+  if (strcmp(name, "count_wrapped_workgroups") == 0) {  // pass-B workgroups of the last pengk_count that recounted their slices exactly
+    uint32_t n = 0;
+    if (ctx->d_wrap_count) {
+      PENGK_HIP(hipMemcpyAsync(&n, ctx->d_wrap_count, sizeof n, hipMemcpyDeviceToHost, ctx->stream));
+      PENGK_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    *value = n;
+    return PENGK_OK;
+  }
+  if (strcmp(name, "count_group") == 0) {  // the option, as set
+    *value = ctx->count_group;
+    return PENGK_OK;
+  }
+  if (strcmp(name, "count_group_used") == 0) {  // keys per group of the emitter the last pengk_count ran (0: not the one-level partition)
+    *value = ctx->count_group_used;
+    return PENGK_OK;
+  }
+  if (strcmp(name, "count_slices") == 0) {  // test hook: (wave, bucket) slices of the last one-level partitioned count
+    *value = ctx->d_slice_fill ? (int64_t)ctx->n_slice_fill : 0;
+    return PENGK_OK;
+  }
+  if (strcmp(name, "count_slice_fill") == 0) {  // test hook: entries pass A published for slice "count_probe_slice"
+    if (!ctx->d_slice_fill || ctx->count_probe_slice >= ctx->n_slice_fill)
+      return fail(PENGK_ERR_ARG, "count_slice_fill: the last count has no slice %llu", (unsigned long long)ctx->count_probe_slice);
+    uint32_t n = 0;
+    PENGK_HIP(hipMemcpyAsync(&n, ctx->d_slice_fill + ctx->count_probe_slice, sizeof n, hipMemcpyDeviceToHost, ctx->stream));
+    PENGK_HIP(hipStreamSynchronize(ctx->stream));
     *value = n;
     return PENGK_OK;
   }

@@ -407,6 +407,11 @@ __global__ __launch_bounds__(256) void count_kernel(const uint32_t* __restrict__
 // ---------------------------------------------------------------------------------------------
 constexpr int RING_CAP = 128;           // u16 entries per (wave, bucket) ring: a group of 64 plus 64 in flight
 constexpr int GROUP = RING_CAP / 2;        // entries written per flush (one 128-byte line at RING_CAP = 128)
+// Invariant of a ring of 2 G entries that leaves in groups of G (G = 64 here; G = 128 with 256-entry rings at W = 10 on
+// both strands): a step of the scan appends at most 64 keys to one ring -- one per lane -- and every completed group
+// is flushed in the step that completed it.  So a ring holds at most G - 1 pending entries when a step begins, and
+// (G - 1) + 64 < 2 G: no entry of an unflushed group is overwritten; and as 64 <= G, two groups of one ring cannot
+// complete in one step.
 constexpr uint32_t KEY_INVALID = 0xFFFFu;
 constexpr int PAYLOAD_BITS = 15;
 
@@ -510,24 +515,23 @@ struct Split14L3 {
 // One row per (wave, bucket): the ring and, behind it, its counter.  The odd row stride (65 dwords) spreads rows over
 // the LDS banks: rings fill at the same pace, and with a 256-byte stride equal fill levels would put every lane of
 // the 16-bit ring write -- and every counter -- on the same few banks.
-template <class E>  // E = uint16_t (15-bit payloads) or uint32_t (the 19-bit payloads of W = 12's first level)
+template <class E, int CAP = RING_CAP>  // E = uint16_t (15- or 16-bit payloads) or uint32_t (the 19-bit payloads of W = 12's first level)
 struct ScatterRowT {
-  E ring[RING_CAP];
-  uint32_t fill4;  // 4 x (keys ever appended to this (wave, bucket))
+  E ring[CAP];
+  uint32_t fill4;  // STEP x (keys ever appended to this (wave, bucket)), STEP = 256 / group: 4 x at groups of 64 (the name), 2 x at 128
 };
-typedef ScatterRowT<uint16_t> ScatterRow;
-template <int NBITS, int WPW, class E = uint16_t>
+template <int NBITS, int WPW, class E = uint16_t, int CAP = RING_CAP>
 struct ScatterShared {
   static constexpr int NB = 1 << NBITS;
-  ScatterRowT<E> row[WPW][NB];
+  ScatterRowT<E, CAP> row[WPW][NB];
 };
 
 // The one LDS instance per workgroup.  It is reached through this accessor, never through a pointer
 // stored in a struct: a generic pointer made the compiler emit flat_load for the ring reads, and a flat
 // access waits for vmcnt(0) -- i.e. for every key store still in flight -- on every flush.
-template <int NBITS, int WPW, class E = uint16_t>
-__device__ __forceinline__ ScatterShared<NBITS, WPW, E>& scatter_lds() {
-  __shared__ ScatterShared<NBITS, WPW, E> sh;
+template <int NBITS, int WPW, class E = uint16_t, int CAP = RING_CAP>
+__device__ __forceinline__ ScatterShared<NBITS, WPW, E, CAP>& scatter_lds() {
+  __shared__ ScatterShared<NBITS, WPW, E, CAP> sh;
   return sh;
 }
 
@@ -542,52 +546,71 @@ __device__ __forceinline__ ScatterShared<NBITS, WPW, E>& scatter_lds() {
 // a group" is ONE sub-dword compare, and (value >> 1) & 0xFF is the byte offset of the key's ring entry.  A
 // suppressed window arrives as INVALID_ID: its bucket bits select the last bucket and its payload bits are
 // KEY_INVALID, which pass B skips -- no select, no sink row (7 vector instructions per key instead of 14).
-template <class KS, int NBITS, int WPW = 4, class E = uint16_t>
+//
+// Groups of 128 (G = 128: 16-bit entries, 256-entry rings, W = 10 on both strands): the same scheme at half the flush
+// events per key.  The counter advances by 2 per key: byte 0 is 2 * (slot mod 128), "completes a group" is byte 0 ==
+// 254, and value & 511 is the byte offset of the key's ring entry.  A flush moves one DWORD -- two keys -- per lane:
+// 256 contiguous bytes.  The 16-bit payload IS the key, so there is no entry that pass B could skip: a suppressed
+// window travels as the ordinary key (last bucket, payload 0xFFFF) of the canonical id 4^W - 1 (poly-T), which never
+// occurs on both strands (its reverse complement 0 is smaller) -- pass C stores 0 in that bin; drain() pads nothing and
+// publishes the EXACT number of valid entries of a slice, beyond which pass B reads nothing.
+template <class KS, int NBITS, int WPW = 4, class E = uint16_t, int G = GROUP>
 struct ScatterEmit {
   static constexpr int NB = 1 << NBITS;
+  static constexpr int CAP = 2 * G;                              // ring entries: a group and what is appended while it completes
   static constexpr uint32_t ES = (uint32_t)sizeof(E);           // bytes per ring / slice entry
   static constexpr uint32_t ESH = ES == 2u ? 1u : 2u;            // log2(ES)
-  static constexpr uint32_t PAD = ES == 2u ? KEY_INVALID : 0xFFFFFFFFu;  // an entry pass B / the next level skips
-  typedef ScatterRowT<E> Row;
-  static_assert(GROUP == 64, "a group is one entry per lane");
-  static_assert(RING_CAP == 128, "byte 0 of the counter addresses the ring");
+  static constexpr uint32_t STEP = 256u / (uint32_t)G;           // the counter's advance per key: byte 0 = STEP * (slot mod G)
+  static constexpr uint32_t SSH = G == 64 ? 2u : 1u;             // log2(STEP)
+  static constexpr uint32_t MV = ES * (uint32_t)G / 64u;         // bytes a lane moves per flush
+  static constexpr uint32_t PAD = ES == 2u ? KEY_INVALID : 0xFFFFFFFFu;  // an entry pass B / the next level skips (G = 64)
+  typedef ScatterRowT<E, CAP> Row;
+  static_assert(G == 64 || (G == 128 && ES == 2u), "a group is one entry, or one dword of two 16-bit entries, per lane");
+  static_assert(STEP * (uint32_t)G == 256u, "byte 0 of the counter addresses the group");
   E* __restrict__ keys;
-  uint32_t slice_cap;  // entries per (wave, bucket) slice, multiple of 64; NB * slice_cap * ES < 2^32
-  uint32_t* __restrict__ slice_fill;  // [n_waves][NB] entries written (multiple of 64)
+  uint32_t slice_cap;  // entries per (wave, bucket) slice, multiple of G; NB * slice_cap * ES < 2^32
+  uint32_t* __restrict__ slice_fill;  // [n_waves][NB] entries written (G = 64: a multiple of 64; G = 128: the valid ones, exactly)
   uint32_t* __restrict__ hist;
   uint32_t wave, lane, wave_global;   // wave, wave_global: wave-uniform (readfirstlane'd by the caller)
   uint32_t outer;     // level-1 bucket these keys came from (two-level partition); 0 otherwise
 
   // All threads of the workgroup, before the first barrier: rings all ones, counters 0.
   static __device__ __forceinline__ void init_lds() {
-    ScatterShared<NBITS, WPW, E>& sh = scatter_lds<NBITS, WPW, E>();
-    static_assert(sizeof(Row) == ES * RING_CAP + 4, "row = ring + counter");
+    ScatterShared<NBITS, WPW, E, CAP>& sh = scatter_lds<NBITS, WPW, E, CAP>();
+    static_assert(sizeof(Row) == ES * CAP + 4, "row = ring + counter");
+    static_assert((sizeof(Row) / 4u) % 2u == 1u, "odd row stride in dwords");
     uint32_t* w = reinterpret_cast<uint32_t*>(&sh.row[0][0]);
     for (uint32_t i = threadIdx.x; i < (uint32_t)WPW * NB * (sizeof(Row) / 4u); i += blockDim.x)
-      w[i] = (i % (uint32_t)(sizeof(Row) / 4u)) == (uint32_t)(ES * RING_CAP / 4u) ? 0u : 0xFFFFFFFFu;
+      w[i] = (i % (uint32_t)(sizeof(Row) / 4u)) == (uint32_t)(ES * CAP / 4u) ? 0u : 0xFFFFFFFFu;
   }
 
   typedef __attribute__((address_space(3))) uint32_t lds_u32_t;
   typedef __attribute__((address_space(3))) E lds_e_t;
   typedef __attribute__((address_space(1))) E global_e_t;
+  typedef __attribute__((address_space(1))) uint32_t global_u32_t;
 
-  // A completed group (64 ring entries from slot g0, a multiple of 64) goes to slice entries [g0, g0 + 64) as ONE
-  // line (128 bytes of 16-bit entries, 256 of 32-bit ones), one load and store per lane.  Everything wave-uniform about
+  // A completed group (G ring entries from slot g0, a multiple of G) goes to slice entries [g0, g0 + G) as ONE line
+  // (G = 64: 128 bytes of 16-bit entries, 256 of 32-bit ones; G = 128: 256 bytes of 16-bit entries, a dword of two per
+  // lane), one load and store per lane.  (The names s4, g4, c4 are the 64-key form's: they hold STEP x a slot, 4 x at
+  // G = 64 and 2 x at G = 128.)  Everything wave-uniform about
   // a group -- where it starts in the ring, where it goes in the wave's key region, whether the slice still has room --
   // is computed by the lane whose key completed it, with a handful of vector instructions that all lanes run side by
   // side; the loop then needs two v_readlane per group and no scalar multiply / shift / mask chain (13 instruction
   // issues per group instead of 30; the flush was half of what this kernel issues).
-  __device__ __forceinline__ void flush_triggered(unsigned long long trig, uint32_t row, uint32_t b, uint32_t s4) {
+  // (s4: the counter value the completing key got, STEP x its slot; nvalid, G = 128 only: the group's valid entries --
+  // G, or what a partial last group holds, which counts if the slice has no room for it)
+  __device__ __forceinline__ void flush_triggered(unsigned long long trig, uint32_t row, uint32_t b, uint32_t s4,
+                                                  uint32_t nvalid = (uint32_t)G) {
     // (an empty asm: the compiler must not fold the caller's wave-uniform "some key completed a group" branch into the
     // masks below -- that turns one scalar branch per key into five scalar instructions)
     asm volatile("");
-    const uint32_t g4 = s4 - 4u * (uint32_t)(GROUP - 1);        // 4 x first slot of the group (in trigger lanes)
-    const uint32_t src = row + ((g4 >> (2u - ESH)) & (ES * (uint32_t)GROUP));  // ring byte offset: first or second half
-    const uint32_t dst = b * (ES * slice_cap) + (g4 >> (2u - ESH));  // byte offset in the wave's region
-    const unsigned long long fits = __builtin_amdgcn_ballot_w64(g4 + 4u * GROUP <= 4u * slice_cap);
+    const uint32_t g4 = s4 - STEP * (uint32_t)(G - 1);          // STEP x first slot of the group (in trigger lanes)
+    const uint32_t src = row + ((g4 >> (SSH - ESH)) & (ES * (uint32_t)G));  // ring byte offset: first or second half
+    const uint32_t dst = b * (ES * slice_cap) + (g4 >> (SSH - ESH));  // byte offset in the wave's region
+    const unsigned long long fits = __builtin_amdgcn_ballot_w64(g4 + STEP * G <= STEP * slice_cap);
     unsigned long long todo = trig & fits;
     unsigned long long over = trig & ~fits;
-    while (todo) {  // wave-uniform: on average one group per step
+    while (todo) {  // wave-uniform: on average one group per step (per two steps at G = 128)
       const int p = __builtin_ctzll(todo);
       todo &= todo - 1;
       const uint32_t s_src = (uint32_t)__builtin_amdgcn_readlane((int)src, p);
@@ -595,18 +618,34 @@ struct ScatterEmit {
       // A plain LDS load (a volatile one makes the compiler drain lgkmcnt(0) in front of it).  The LDS executes a wave's
       // operations in order, so it sees every ring write issued before it; ring writes through integer-formed addresses
       // lie between two reads of a location, so it cannot be satisfied from an older copy.
-      uint32_t v = *(lds_e_t*)(uintptr_t)(s_src + ES * lane);
-      asm volatile("" : "+v"(v));  // consumed here on every path: no wait for it leaks into the next window's code
-      global_e_t* out = (global_e_t*)((char*)region + s_dst);
-      __builtin_nontemporal_store((E)v, &out[lane]);  // written once, read once by the next pass
+      if constexpr (MV == ES) {
+        uint32_t v = *(lds_e_t*)(uintptr_t)(s_src + ES * lane);
+        asm volatile("" : "+v"(v));  // consumed here on every path: no wait for it leaks into the next window's code
+        global_e_t* out = (global_e_t*)((char*)region + s_dst);
+        __builtin_nontemporal_store((E)v, &out[lane]);  // written once, read once by the next pass
+      } else {  // two 16-bit entries per lane (rows, ring halves and slices all start on multiples of four bytes)
+        uint32_t v = *(lds_u32_t*)(uintptr_t)(s_src + 4u * lane);
+        asm volatile("" : "+v"(v));
+        global_u32_t* out = (global_u32_t*)((char*)region + s_dst);
+        __builtin_nontemporal_store(v, &out[lane]);
+      }
     }
     while (over) {  // slice full: count these windows directly (rare; skewed inputs)
       const int p = __builtin_ctzll(over);
       over &= over - 1;
       const uint32_t s_src = (uint32_t)__builtin_amdgcn_readlane((int)src, p);
       const uint32_t fb = (uint32_t)__builtin_amdgcn_readlane((int)b, p);
-      const uint32_t v = *(lds_e_t*)(uintptr_t)(s_src + ES * lane);
-      if (KS::valid(v)) __hip_atomic_fetch_add(&hist[KS::join(fb, v, outer)], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if constexpr (MV == ES) {
+        const uint32_t v = *(lds_e_t*)(uintptr_t)(s_src + ES * lane);
+        if (KS::valid(v)) __hip_atomic_fetch_add(&hist[KS::join(fb, v, outer)], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      } else {  // every entry in front of nvalid is a key
+        const uint32_t nv = (uint32_t)__builtin_amdgcn_readlane((int)nvalid, p);
+        const uint32_t v = *(lds_u32_t*)(uintptr_t)(s_src + 4u * lane);
+        if (2u * lane < nv)
+          __hip_atomic_fetch_add(&hist[KS::join(fb, v & 0xFFFFu, outer)], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (2u * lane + 1u < nv)
+          __hip_atomic_fetch_add(&hist[KS::join(fb, v >> 16, outer)], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
     }
   }
 
@@ -615,18 +654,18 @@ struct ScatterEmit {
   // compiler otherwise re-materialises the scalar base with a v_mov per key).
   uint32_t rowbase = 0;
   __device__ __forceinline__ void bind() {
-    rowbase = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)&scatter_lds<NBITS, WPW, E>().row[wave][0];
+    rowbase = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)&scatter_lds<NBITS, WPW, E, CAP>().row[wave][0];
     asm volatile("" : "+v"(rowbase));
     region = keys + (size_t)wave_global * NB * slice_cap;
   }
   E* region = nullptr;  // this wave's key region (wave-uniform): NB slices of slice_cap entries
 
-  // append one key per lane: the row of its bucket (returned through `row`) and 4 x its slot
+  // append one key per lane: the row of its bucket (returned through `row`) and STEP x its slot
   __device__ __forceinline__ uint32_t append(uint32_t b, uint32_t key, uint32_t& row) const {
     row = b * (uint32_t)sizeof(Row) + rowbase;  // b < NB: one v_mad_u32_u24
-    const uint32_t s4 = __hip_atomic_fetch_add((lds_u32_t*)(uintptr_t)(row + ES * RING_CAP), 4u, __ATOMIC_RELAXED,
+    const uint32_t s4 = __hip_atomic_fetch_add((lds_u32_t*)(uintptr_t)(row + ES * CAP), STEP, __ATOMIC_RELAXED,
                                                __HIP_MEMORY_SCOPE_WORKGROUP);
-    *(lds_e_t*)(uintptr_t)(row + ((s4 >> (2u - ESH)) & (ES * RING_CAP - 1u))) = (E)KS::payload(key);
+    *(lds_e_t*)(uintptr_t)(row + ((s4 >> (SSH - ESH)) & (ES * CAP - 1u))) = (E)KS::payload(key);
     return s4;
   }
 
@@ -635,7 +674,7 @@ struct ScatterEmit {
     const uint32_t b = KS::bucket(key);
     uint32_t row;
     const uint32_t s4 = append(b, key, row);
-    const unsigned long long trig = __builtin_amdgcn_ballot_w64((s4 & 0xFFu) == 4u * (uint32_t)(GROUP - 1));
+    const unsigned long long trig = __builtin_amdgcn_ballot_w64((s4 & 0xFFu) == STEP * (uint32_t)(G - 1));
     if (trig) flush_triggered(trig, row, b, s4);  // wave-uniform
   }
 
@@ -644,32 +683,39 @@ struct ScatterEmit {
     const uint32_t b = KS::bucket(key);
     uint32_t s4 = 0, row = 0;
     if (active) s4 = append(b, key, row);
-    const unsigned long long trig = __builtin_amdgcn_ballot_w64(active && (s4 & 0xFFu) == 4u * (uint32_t)(GROUP - 1));
+    const unsigned long long trig = __builtin_amdgcn_ballot_w64(active && (s4 & 0xFFu) == STEP * (uint32_t)(G - 1));
     if (trig) flush_triggered(trig, row, b, s4);
   }
 
-  // end of kernel: lane b pads bucket b's last, partial group with all-ones entries -- appending the padding, so that
-  // the group is complete and leaves like every other -- and publishes how much of the slice is filled
+  // end of kernel: lane b completes bucket b's last, partial group, so that it leaves as a line like every other, and
+  // publishes how much of the slice is filled.  G = 64: the group is padded with all-ones entries, which the next pass
+  // skips, and the fill counts them.  G = 128: nothing marks an entry as padding -- what lies behind the group's valid
+  // entries leaves as it stands in the ring, and the fill is the EXACT number of valid entries (at most what the slice
+  // holds: keys beyond it were counted directly), beyond which pass B reads nothing.
   __device__ __forceinline__ void drain() {
     __builtin_amdgcn_wave_barrier();
-    uint32_t row = 0, s4_last = 0;
+    uint32_t row = 0, s4_last = 0, nvalid = 0;
     bool padded = false;
     if (lane < (uint32_t)NB) {
       row = lane * (uint32_t)sizeof(Row) + rowbase;
-      const uint32_t c4 = __hip_atomic_load((lds_u32_t*)(uintptr_t)(row + ES * RING_CAP), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-      const uint32_t r = (c4 >> 2) & (uint32_t)(GROUP - 1);
+      const uint32_t c4 = __hip_atomic_load((lds_u32_t*)(uintptr_t)(row + ES * CAP), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+      const uint32_t r = (c4 >> SSH) & (uint32_t)(G - 1);
       if (r) {
-        for (uint32_t i = r; i < (uint32_t)GROUP; ++i)
-          *(lds_e_t*)(uintptr_t)(row + (((c4 >> (2u - ESH)) & (ES * RING_CAP - 1u)) + ES * (i - r))) = (E)PAD;
-        s4_last = c4 + 4u * ((uint32_t)GROUP - r) - 4u;  // the slot value the completing key would have got
+        if constexpr (G == 64) {
+          for (uint32_t i = r; i < (uint32_t)G; ++i)
+            *(lds_e_t*)(uintptr_t)(row + (((c4 >> (SSH - ESH)) & (ES * CAP - 1u)) + ES * (i - r))) = (E)PAD;
+        }
+        s4_last = c4 + STEP * ((uint32_t)G - r) - STEP;  // the counter value the completing key would have got
+        nvalid = r;
         padded = true;
       }
-      const uint32_t full = ((c4 >> 2) + (uint32_t)(GROUP - 1)) & ~(uint32_t)(GROUP - 1);
+      // (slice_cap is a multiple of G: a group lies in the slice or behind it, never across its end)
+      const uint32_t full = G == 64 ? ((c4 >> SSH) + (uint32_t)(G - 1)) & ~(uint32_t)(G - 1) : c4 >> SSH;
       slice_fill[(size_t)wave_global * NB + lane] = full < slice_cap ? full : slice_cap;
     }
     __builtin_amdgcn_wave_barrier();
     const unsigned long long trig = __builtin_amdgcn_ballot_w64(padded);
-    if (trig) flush_triggered(trig, row, lane, s4_last);
+    if (trig) flush_triggered(trig, row, lane, s4_last, nvalid);
   }
 };
 
@@ -679,11 +725,16 @@ struct ScatterEmit {
 constexpr int SCATTER_WPW = PENGK_SCATTER_WPW;  // waves per workgroup of pass A
 // The one-level scheme (W = 8, 10) lets a full slice's keys overflow into the bucket-major table `temp` that pass B adds
 // its histograms to, at the index pass C reads: the final table is then written once, by pass C, and needs no clear.
+// The payload has PBITS = 2 W - NBITS bits: 15 (32 buckets at W = 10, 2 at W = 8: groups of 64, the entry 0xFFFF marks what
+// pass B skips) or 16 (16 buckets at W = 10 on both strands: groups of 128, the payload is the whole u16 key).
 template <int W, int NBITS>
 struct KeySplitTemp : KeySplit<W, NBITS> {
-  __host__ __device__ static inline uint32_t join(uint32_t b, uint32_t p, uint32_t /*outer*/ = 0) { return (b << PAYLOAD_BITS) | p; }
+  static constexpr int PBITS = 2 * W - NBITS;
+  static constexpr int G = PBITS == 16 ? 128 : GROUP;  // keys per group of the emitter that goes with this split
+  static_assert(PBITS == PAYLOAD_BITS || (PBITS == 16 && W == 10), "15-bit payloads, or 16-bit ones at W = 10");
+  __host__ __device__ static inline uint32_t join(uint32_t b, uint32_t p, uint32_t /*outer*/ = 0) { return (b << PBITS) | p; }
   __host__ __device__ static inline uint32_t index(uint32_t id) {
-    return (KeySplit<W, NBITS>::bucket(id) << PAYLOAD_BITS) | KeySplit<W, NBITS>::payload(id);
+    return (KeySplit<W, NBITS>::bucket(id) << PBITS) | KeySplit<W, NBITS>::payload(id);
   }
 };
 template <int W, bool BOTH, int NBITS, bool BG>
@@ -695,8 +746,11 @@ __global__ __launch_bounds__(64 * SCATTER_WPW) void count_scatter_kernel(const u
                                                             uint32_t* __restrict__ defer_count,
                                                             uint32_t* __restrict__ defer_list,
                                                             uint32_t* __restrict__ bg_partials) {
-  static_assert(2 * W - NBITS == PAYLOAD_BITS, "payload must be 15 bits");
-  typedef ScatterEmit<KeySplitTemp<W, NBITS>, NBITS, SCATTER_WPW> Emit;
+  typedef KeySplitTemp<W, NBITS> KS;
+  // 16-bit payloads leave no entry to mark a suppressed window: it travels as the key of the canonical id 4^W - 1
+  // (poly-T), which occurs on one strand and never on both (its reverse complement 0 is smaller)
+  static_assert(KS::PBITS == PAYLOAD_BITS || BOTH, "the 16-bucket split needs both strands");
+  typedef ScatterEmit<KS, NBITS, SCATTER_WPW, uint16_t, KS::G> Emit;
   Emit::init_lds();
   bg_begin<BG>();
   __syncthreads();
@@ -917,6 +971,114 @@ __device__ __forceinline__ void hist_block(uint32_t* __restrict__ h, uint32_t bl
   }
 }
 
+// Pass B over 16-bit keys (the 16-bucket split: W = 10 on both strands): a bucket has 2^16 bins, and the workgroup keeps
+// them as 16-bit halves packed in the same 2^15 LDS words -- key k adds 1 << 16 (k >> 15) to word k & 0x7FFF with a
+// plain, non-returning LDS add: as many LDS atomics per key as hist_block, and no validity test (every entry in front of
+// a slice's exact fill is a key; only the slice's last, partial 16-byte vector is predicated, by index).
+//
+// A half that collects 2^16 keys or more wraps.  That is checked ONCE, after the barrier and before anything goes to the
+// global table: N = the keys the workgroup counted (the sum of its slices' fills), S = the sum over all words of (low
+// half + high half).  If no half reached 2^16, every half is its true count and S = N.  Otherwise a low half that
+// wraps carries 1 into its neighbour and loses 65536, and a high half that wraps loses 65536: every wrap makes S smaller
+// and none makes it larger, so S = N exactly when no half wrapped.  Then the halves are added to the bucket-major table;
+// otherwise the workgroup discards its bins, reads its own slices again and adds every key to the table with
+// device-scope atomics: slow and exact (what an overflowed slice does in pass A), a workgroup-uniform branch on an LDS
+// broadcast, nothing between workgroups.  `wrapped` counts the workgroups that took it.
+__device__ __forceinline__ void hist16_block(uint32_t* __restrict__ h, uint32_t block, const uint16_t* __restrict__ keys,
+                                             uint32_t slice_cap, uint32_t n_slices, uint32_t nb,
+                                             const uint32_t* __restrict__ slice_fill, uint32_t bpb,
+                                             uint32_t* __restrict__ temp, uint32_t* __restrict__ wrapped) {
+  __shared__ unsigned long long sums[2];  // N, S
+  const uint32_t b = block / bpb, j = block % bpb;
+  for (uint32_t i = threadIdx.x; i < (1u << 15); i += blockDim.x) h[i] = 0;
+  if (threadIdx.x < 2) sums[threadIdx.x] = 0;
+  __syncthreads();
+  const uint32_t per = (n_slices + bpb - 1) / bpb;
+  const uint32_t first = j * per, last = min(n_slices, j * per + per);
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  auto add2 = [&](uint32_t x) {  // the two keys of a dword
+    atomicAdd(&h[x & 0x7FFFu], 1u << ((x >> 11) & 16u));
+    atomicAdd(&h[(x >> 16) & 0x7FFFu], 1u << ((x >> 27) & 16u));
+  };
+  auto count8 = [&](const u32x4& v) {
+    add2(v.x);
+    add2(v.y);
+    add2(v.z);
+    add2(v.w);
+  };
+  unsigned long long n_keys = 0;  // (wave-uniform)
+  uint32_t fill_next = first + wave < last ? slice_fill[(size_t)(first + wave) * nb + b] : 0u;
+  for (uint32_t s = first + wave; s < last; s += 16) {
+    const uint32_t fill = fill_next;  // valid entries, exactly (<= slice_cap)
+    const uint32_t n8 = fill >> 3;    // whole 16-byte vectors
+    if (s + 16 < last) fill_next = slice_fill[(size_t)(s + 16) * nb + b];
+    n_keys += fill;
+    const u32x4* src = reinterpret_cast<const u32x4*>(keys + ((size_t)s * nb + b) * slice_cap);  // (slice_cap: a multiple of 128)
+    uint32_t i = lane;
+    for (; i + 448 < n8; i += 512) {  // eight 16-byte loads in flight per lane before their 64 LDS adds
+      u32x4 v[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) v[q] = __builtin_nontemporal_load(&src[i + 64 * q]);  // streamed once
+#pragma unroll
+      for (int q = 0; q < 8; ++q) count8(v[q]);
+    }
+    // the rest: up to seven whole vectors per lane and, in lane 0, the slice's last, partial one -- all in flight together
+    const uint32_t part = fill & 7u;
+    const bool has_part = part != 0u && lane == 0u;
+    u32x4 vp = {0u, 0u, 0u, 0u};
+    if (has_part) vp = __builtin_nontemporal_load(&src[n8]);  // (inside the slice: fill <= slice_cap, a multiple of 8)
+    if (i < n8) {
+      u32x4 v[7];
+#pragma unroll
+      for (int q = 0; q < 7; ++q) {
+        const u32x4 zero = {0u, 0u, 0u, 0u};
+        v[q] = i + 64u * q < n8 ? __builtin_nontemporal_load(&src[i + 64 * q]) : zero;
+      }
+#pragma unroll
+      for (int q = 0; q < 7; ++q)
+        if (i + 64u * q < n8) count8(v[q]);
+    }
+    if (has_part) {
+      const uint32_t w[4] = {vp.x, vp.y, vp.z, vp.w};
+#pragma unroll
+      for (uint32_t q = 0; q < 7u; ++q) {
+        const uint32_t k = (w[q >> 1] >> (16u * (q & 1u))) & 0xFFFFu;
+        if (q < part) atomicAdd(&h[k & 0x7FFFu], 1u << ((k >> 11) & 16u));
+      }
+    }
+  }
+  if (lane == 0 && n_keys) atomicAdd(&sums[0], n_keys);
+  __syncthreads();
+  {
+    unsigned long long sum = 0;
+    for (uint32_t i = threadIdx.x; i < (1u << 15); i += blockDim.x) {
+      const uint32_t v = h[i];
+      sum += (v & 0xFFFFu) + (v >> 16);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off, 64);
+    if (lane == 0 && sum) atomicAdd(&sums[1], sum);
+  }
+  __syncthreads();
+  uint32_t* dst = temp + ((size_t)b << 16);
+  if (sums[0] == sums[1]) {  // (workgroup-uniform) no half wrapped: every half is a count
+    for (uint32_t i = threadIdx.x; i < (1u << 15); i += blockDim.x) {
+      const uint32_t v = h[i];
+      if (v & 0xFFFFu) __hip_atomic_fetch_add(&dst[i], v & 0xFFFFu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (v >> 16) __hip_atomic_fetch_add(&dst[0x8000u | i], v >> 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    return;
+  }
+  if (threadIdx.x == 0) __hip_atomic_fetch_add(wrapped, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  for (uint32_t s = first + wave; s < last; s += 16) {
+    const uint32_t fill = slice_fill[(size_t)s * nb + b];
+    const uint16_t* src = keys + ((size_t)s * nb + b) * slice_cap;
+    for (uint32_t i = lane; i < fill; i += 64)
+      __hip_atomic_fetch_add(&dst[src[i]], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
 __global__ __launch_bounds__(1024) void count_hist_kernel(const uint16_t* __restrict__ keys, uint32_t slice_cap,
                                                           uint32_t n_slices, uint32_t nb,
                                                           const uint32_t* __restrict__ slice_fill, uint32_t bpb,
@@ -946,7 +1108,12 @@ __global__ __launch_bounds__(256) void count_gather_kernel(const uint32_t* __res
                                                            unsigned long long* __restrict__ ltot) {
   using KS = KeySplitTemp<W, NBITS>;
   if (blockIdx.x == 0 && threadIdx.x == 0) *ltot = *ltot_acc;
-  for (uint32_t x = blockIdx.x * blockDim.x + threadIdx.x; x < np; x += gridDim.x * blockDim.x) hist[x] = temp[KS::index(x)];
+  for (uint32_t x = blockIdx.x * blockDim.x + threadIdx.x; x < np; x += gridDim.x * blockDim.x) {
+    uint32_t v = temp[KS::index(x)];
+    // 16-bit payloads: the last bin (poly-T, which both strands never count) collected the suppressed windows
+    if (KS::PBITS == 16 && x == np - 1u) v = 0;
+    hist[x] = v;
+  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1194,8 +1361,9 @@ __global__ __launch_bounds__(1024) void count_hist_front_kernel(const uint16_t* 
                                                                 const uint32_t* __restrict__ words32,
                                                                 const uint64_t* __restrict__ items, int both,
                                                                 const uint32_t* __restrict__ defer_count,
-                                                                const uint32_t* __restrict__ defer_list, uint32_t n_fix) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t h[];  // 2^15 bins
+                                                                const uint32_t* __restrict__ defer_list, uint32_t n_fix,
+                                                                uint32_t* __restrict__ wrapped) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t h[];  // 2^15 bins (2^16 packed halves for 16-bit payloads)
   if (blockIdx.x == 0) {
     if (bg_out) bg_finish_block(reinterpret_cast<unsigned long long*>(h), bg_partials, bg_blocks, bg_out);
     return;
@@ -1209,7 +1377,10 @@ __global__ __launch_bounds__(1024) void count_hist_front_kernel(const uint16_t* 
                 });
     return;
   }
-  hist_block(h, blockIdx.x - 1u - n_fix, keys, slice_cap, n_slices, 1u << NBITS, slice_fill, bpb, temp, 0u);
+  if constexpr (KeySplitTemp<W, NBITS>::PBITS == 16)
+    hist16_block(h, blockIdx.x - 1u - n_fix, keys, slice_cap, n_slices, 1u << NBITS, slice_fill, bpb, temp, wrapped);
+  else
+    hist_block(h, blockIdx.x - 1u - n_fix, keys, slice_cap, n_slices, 1u << NBITS, slice_fill, bpb, temp, 0u);
 }
 
 // BackgroundModel::calculateV (src/shared/BackgroundModel.cpp:490-530), one thread, float32 in the
@@ -1348,32 +1519,34 @@ int launch_direct_w(pengk_ctx* ctx, int both, uint32_t* d_counts, uint64_t* d_lt
 }
 
 // W = 8, 10.  One clear and three kernels: launch_count leaves the defer counter, the table and ltot alone for this path.
-template <int W>
+// NBITS = 2 W - 15: groups of 64 keys of 15 bits; NBITS = 4 at W = 10 (both strands only): groups of 128 keys of 16 bits.
+template <int W, int NBITS = 2 * W - PAYLOAD_BITS>
 int launch_partition_w(pengk_ctx* ctx, int both, uint32_t* d_counts, uint64_t* d_ltot, uint32_t n_items, uint64_t* d_bg) {
-  constexpr int NBITS = 2 * W - PAYLOAD_BITS;
+  typedef KeySplitTemp<W, NBITS> KS;
+  constexpr uint32_t GRP = (uint32_t)KS::G;  // keys per group of the emitter
   constexpr uint32_t NB = 1u << NBITS;
   const uint32_t np = 1u << (2 * W);
   const uint32_t* w32 = (const uint32_t*)ctx->d_words;
   // grid of pass A: as many workgroups per CU as the LDS admits (8.3 KiB of rings per wave at NB = 32)
   constexpr uint32_t TPB = 64u * SCATTER_WPW;
   const uint32_t blocks_needed = (n_items + TPB - 1) / TPB;
-  constexpr uint32_t lds_per_wg = (uint32_t)(sizeof(ScatterShared<NBITS, SCATTER_WPW>) + sizeof(BgLds) + 511u) & ~511u;
+  constexpr uint32_t lds_per_wg = (uint32_t)(sizeof(ScatterShared<NBITS, SCATTER_WPW, uint16_t, 2 * KS::G>) + sizeof(BgLds) + 511u) & ~511u;
   const uint32_t per_cu = ctx->scatter_blocks_per_cu ? (uint32_t)ctx->scatter_blocks_per_cu : (160u * 1024u) / lds_per_wg;
   const uint32_t max_blocks = (uint32_t)ctx->num_cu * per_cu;
   const uint32_t blocks = blocks_needed < max_blocks ? blocks_needed : max_blocks;
   const uint32_t n_waves = blocks * (uint32_t)SCATTER_WPW;
-  // static slices region[wave][bucket]: expected share + 50 % + slack, in groups of 64 entries
+  // static slices region[wave][bucket]: expected share + 50 % + slack, in whole groups
   uint64_t windows = ctx->n_windows_hint ? ctx->n_windows_hint : ctx->n_items * (uint64_t)ctx->item_windows;
   const uint64_t share = windows / ((uint64_t)NB * n_waves);
   uint64_t cap64 = share + share / 2 + 512;  // 1.5x the uniform share: real genomes are not uniform
   if (ctx->key_cap_override) cap64 = ctx->key_cap_override;  // test hook: force slices to overflow
-  cap64 = (cap64 + 63) / 64 * 64;
+  cap64 = (cap64 + GRP - 1) / GRP * GRP;
   if (cap64 * NB >= (1ull << 31))  // byte offsets inside a wave's NB slices are 32-bit
     return fail(PENGK_ERR_RANGE, "shard too large for the partitioned count (slice of %llu keys)", (unsigned long long)cap64);
   const uint32_t slice_cap = (uint32_t)cap64;
   int rc = ensure_scratch(ctx, &ctx->d_keys, &ctx->keys_bytes, (size_t)NB * n_waves * slice_cap * sizeof(uint16_t));
   if (rc) return rc;
-  // aux: slice fills | window total (64 bits), defer counter, pad | bucket-major table.  Only what lies behind the slice
+  // aux: slice fills | window total (64 bits), defer counter, pass B's wrapped workgroups | bucket-major table.  Only what lies behind the slice
   // fills is cleared: drain() writes the fill of every (wave, bucket) of every launched wave, and pass B reads no other.
   const size_t fill_words = ((size_t)NB * n_waves + 63) / 64 * 64;
   constexpr size_t HEAD_WORDS = 4;
@@ -1386,16 +1559,30 @@ int launch_partition_w(pengk_ctx* ctx, int both, uint32_t* d_counts, uint64_t* d
   uint32_t* temp = slice_fill + fill_words + HEAD_WORDS;
   PENGK_HIP(hipMemsetAsync(ltot_acc, 0, (HEAD_WORDS + (size_t)np) * sizeof(uint32_t), ctx->stream));
   ctx->d_defer_count = defer_count;
+  uint32_t* wrapped = slice_fill + fill_words + 3;  // (written by the 16-bucket pass B only)
+  ctx->d_wrap_count = wrapped;
+  ctx->d_slice_fill = slice_fill;
+  ctx->n_slice_fill = (uint64_t)NB * n_waves;
+  ctx->count_group_used = (int)GRP;
   uint16_t* keys = (uint16_t*)ctx->d_keys;
   uint32_t* bgp = nullptr;
   if (d_bg) {
     rc = bg_partials_buffer(ctx, blocks, &bgp);
     if (rc) return rc;
   }
-#define TA_SCATTER(B, G) W, B, NBITS, G
-  PENGK_LAUNCH_BB(count_scatter_kernel, TA_SCATTER, both, d_bg != nullptr, dim3(blocks), dim3(TPB), w32, ctx->d_items, n_items,
-                  keys, slice_cap, slice_fill, temp, ltot_acc, defer_count, ctx->d_defer + 1, bgp);
+  if constexpr (KS::PBITS == 16) {  // both strands only (launch_count_w)
+    if (d_bg)
+      hipLaunchKernelGGL((count_scatter_kernel<W, true, NBITS, true>), dim3(blocks), dim3(TPB), 0, ctx->stream, w32, ctx->d_items,
+                         n_items, keys, slice_cap, slice_fill, temp, ltot_acc, defer_count, ctx->d_defer + 1, bgp);
+    else
+      hipLaunchKernelGGL((count_scatter_kernel<W, true, NBITS, false>), dim3(blocks), dim3(TPB), 0, ctx->stream, w32, ctx->d_items,
+                         n_items, keys, slice_cap, slice_fill, temp, ltot_acc, defer_count, ctx->d_defer + 1, bgp);
+  } else {
+#define TA_SCATTER(B, BG) W, B, NBITS, BG
+    PENGK_LAUNCH_BB(count_scatter_kernel, TA_SCATTER, both, d_bg != nullptr, dim3(blocks), dim3(TPB), w32, ctx->d_items, n_items,
+                    keys, slice_cap, slice_fill, temp, ltot_acc, defer_count, ctx->d_defer + 1, bgp);
 #undef TA_SCATTER
+  }
   PENGK_HIP(hipGetLastError());
   // pass B: one 1024-thread workgroup per CU (128 KiB of LDS), bpb workgroups per bucket; in front of them the
   // workgroup that finishes the fused K1b and those of the fix-up (as many lanes as its stand-alone launch has)
@@ -1408,7 +1595,7 @@ int launch_partition_w(pengk_ctx* ctx, int both, uint32_t* d_counts, uint64_t* d
   constexpr uint32_t N_FIX = 4;
   hipLaunchKernelGGL((count_hist_front_kernel<W, NBITS>), dim3(1u + N_FIX + NB * bpb), dim3(1024), 4 << PAYLOAD_BITS, ctx->stream,
                      keys, slice_cap, n_waves, slice_fill, bpb, temp, bgp, blocks, (unsigned long long*)d_bg, w32, ctx->d_items, both,
-                     defer_count, ctx->d_defer + 1, N_FIX);
+                     defer_count, ctx->d_defer + 1, N_FIX, wrapped);
   PENGK_HIP(hipGetLastError());
   const uint32_t gb = (np + 255) / 256 < 2048u ? (np + 255) / 256 : 2048u;
   hipLaunchKernelGGL((count_gather_kernel<W, NBITS>), dim3(gb), dim3(256), 0, ctx->stream, temp, np, d_counts, ltot_acc,
@@ -1588,6 +1775,14 @@ int launch_count_w(pengk_ctx* ctx, int both, uint32_t* d_counts, uint64_t* d_lto
   constexpr bool can_partition = (W == 8 || W == 10 || W == 12 || W == 14);
   if (impl == 0) impl = can_partition ? 2 : 1;
   if (impl == 2 && !can_partition) return fail(PENGK_ERR_UNSUPPORTED, "partitioned count is built for W = 8 .. 14 only");
+  // groups of 128 keys (16 buckets, 16-bit keys): the one-level partition at W = 10 on both strands, and its default
+  const bool can_group128 = W == 10 && both && impl == 2;
+  if (ctx->count_group == 128 && !can_group128)
+    return fail(PENGK_ERR_UNSUPPORTED, "count_group 128 is built for the partitioned count at W = 10 on both strands only (W = %d, %s, count_impl %d)",
+                W, both ? "both strands" : "one strand", impl);
+  if constexpr (W == 10) {
+    if (can_group128 && ctx->count_group != 64) return launch_partition_w<10, 4>(ctx, both, d_counts, d_ltot, n_items, d_bg);
+  }
   int rc;
   if constexpr (W == 14) {
     rc = impl == 2 ? launch_partition14(ctx, both, d_counts, d_ltot, n_items, d_bg)
@@ -1615,6 +1810,7 @@ int count_init_device() {
   PENGK_HIP(hipFuncSetAttribute((const void*)count_hist_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 4 << PAYLOAD_BITS));
   PENGK_HIP(hipFuncSetAttribute((const void*)count_hist_front_kernel<8, 16 - PAYLOAD_BITS>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 << PAYLOAD_BITS));
   PENGK_HIP(hipFuncSetAttribute((const void*)count_hist_front_kernel<10, 20 - PAYLOAD_BITS>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 << PAYLOAD_BITS));
+  PENGK_HIP(hipFuncSetAttribute((const void*)count_hist_front_kernel<10, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 << PAYLOAD_BITS));
   return PENGK_OK;
 }
 
@@ -1634,6 +1830,9 @@ int launch_count(pengk_ctx* ctx, int both, uint32_t* d_counts, uint64_t* d_ltot,
   // the one-level partition (W = 8, 10) keeps its counters beside its bucket-major table, clears them with it and
   // writes every bin of the table: nothing to clear here
   const bool one_level = (W == 8 || W == 10) && ctx->count_impl != 1 && ctx->n_items > 0;
+  ctx->d_wrap_count = nullptr;  // (the one-level partition sets these)
+  ctx->d_slice_fill = nullptr;
+  ctx->count_group_used = 0;
   if (!one_level) {
     ctx->d_defer_count = ctx->d_defer;
     PENGK_HIP(hipMemsetAsync(ctx->d_defer, 0, sizeof(uint32_t), ctx->stream));

@@ -64,6 +64,12 @@ struct pengk_ctx {
   int em_lean_div = 1;          // K5 serial mode: the weights' divisions without range scaling where a PWM's operand ranges allow (em.hip, lean_div)
   int em_fast = 2;              // K5: 2 = the reference's serial float32 sums, bit-exact (default); 1 = one reciprocal per k-mer weight, 0 = the reference's three divisions
   int count_impl = 0;           // 0 auto, 1 direct atomics, 2 partitioned LDS histograms
+  int count_group = 0;          // keys per group of the partitioned scan's emitter: 0 auto (128 at W = 10 on both strands, else 64), 64, 128
+  int count_group_used = 0;     // ... and what the last count ran with (0: no one-level partition)
+  const uint32_t* d_wrap_count = nullptr;  // where the last count kept the number of pass-B workgroups whose packed bins wrapped (or NULL)
+  const uint32_t* d_slice_fill = nullptr;  // test hook: the last one-level count's slice fills [wave][bucket] (in d_count_aux; or NULL)
+  uint64_t n_slice_fill = 0;               // ... and how many there are
+  uint64_t count_probe_slice = 0;          // ... and the one that the info "count_slice_fill" reads (wave * buckets + bucket)
   int scatter_blocks_per_cu = 0; // tuning hook: workgroups per CU of the partitioned scan (0 = default)
   void* d_sim = nullptr;         // motif similarity grid: PWMs | complements | lengths | sites | scores
   size_t sim_bytes = 0;
