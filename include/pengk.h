@@ -539,6 +539,51 @@ int pengk_site_profiles(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t*
 int pengk_profile_refine(const uint64_t* h_counts, int w, int flank, const float* h_bg, double min_ic, double* h_q,
                          double* h_ic, float* h_pwm, int32_t* first_out, int32_t* last_out, uint64_t* sites_out);
 
+/* ---- first-order motif models (--dinuc: whether neighbouring positions of a found motif depend on each other, and what a
+ *      model that knows it gains; the first step towards the higher-order models BaMMmotif learns from this tool's PWMs;
+ *      INTEGRATION.md 7i) ------------------------------------------------------------------------------------------------
+ * Over the scan layout and the best sites of pengk_motif_best_sites.  Integer up to the counts and again from the
+ * integer log-odds on: any slicing, any rank count and a numpy restatement give the same counts and the same scores; the
+ * model between them is a fixed double-precision formula.  F = min(flank, (PENGK_MAX_MOTIF_LEN - w) / 2) as above. */
+/* Pair profiles: pengk_site_profiles for adjacent pairs.  The same arguments and the same sites.  For every column c in
+ * (-F, w + F), with a the letter at column c - 1 and b the letter at column c, both read on the site's strand exactly as
+ * pengk_site_profiles reads them: ADDS 1 to d_counts[(m * PENGK_MAX_MOTIF_LEN + c + F) * 17 + 4a + b], or to bin 16 of
+ * that row when either position lies outside the sequence or holds another letter.  d_counts: n_motifs x
+ * PENGK_MAX_MOTIF_LEN x 17 uint64, caller-zeroed, accumulating; row 0 of a motif and the rows from w + 2F on stay
+ * untouched.  d_valid = NULL: every base of a sequence is valid. */
+int pengk_site_pair_profiles(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_valid, const int64_t* d_offs,
+                             const uint32_t* d_lens, uint64_t n_seq, int n_motifs, const int32_t* d_best, const uint64_t* d_site,
+                             const int32_t* h_len, const int32_t* h_thr, int flank, uint64_t* d_counts);
+/* Pure CPU.  One motif's first-order model from its counts: h_counts1 the motif's W x 5 rows of pengk_site_profiles,
+ * h_counts2 its W x 17 rows of pengk_site_pair_profiles (same flank, summed over the ranks), W = w + 2F.  h_bg0 (4) and
+ * h_bg1 (16, bg1[4a + b] = P(b | a)) are taken as double and must be > 0; alpha > 0.  In double, in this order, per
+ * column c = 0 .. W - 1:
+ *   n1 = ((k1[0] + k1[1]) + k1[2]) + k1[3] (integers);  q0[c][b] = ((double)k1[b] + bg0[b]) / ((double)n1 + 1.0), b = 0..3
+ *   row[a] = ((k2[4a] + k2[4a+1]) + k2[4a+2]) + k2[4a+3],  col[b] = ((k2[b] + k2[4+b]) + k2[8+b]) + k2[12+b] (integers)
+ *   q1[c][4a+b] = ((double)k2[4a+b] + alpha * q0[c][b]) / ((double)row[a] + alpha) for c >= 1; q1[0][4a+b] = q0[0][b]
+ *   mi[c], c >= 1, N = ((row[0] + row[1]) + row[2]) + row[3]: the sum from 0.0 over a = 0..3, then b = 0..3, of the cells
+ *     with k = k2[4a+b] > 0 of ((double)k / (double)N) * log2(((double)k * (double)N) / ((double)row[a] * (double)col[b]));
+ *     0 when N = 0; mi[0] = 0
+ * and the integer log-odds lo(p, g) = clamp(lround(100 * log2(p / g)), -2000, 2000):
+ *   S0[b] = lo(q0[0][b], bg0[b]);  D1[c][4a+b] = lo(q1[c][4a+b], bg1[4a+b]);  D0[c][4a+b] = lo(q0[c][b], bg1[4a+b]), c >= 1
+ *   (row 0 of D1 and D0 is written as 0).  D0 is the zeroth-order motif over the same first-order background: scored
+ *   with D0 and with D1, the two results differ only by the motif's dependencies.
+ * h_q0 (W x 4), h_q1 (W x 16), h_mi (W), h_S0 (4), h_D1 and h_D0 (W x 16 each), sites_out (the five bins of column F of
+ * h_counts1) may each be NULL. */
+int pengk_dinuc_model(const uint64_t* h_counts1, const uint64_t* h_counts2, int w, int flank, const float* h_bg0,
+                      const float* h_bg1, double alpha, double* h_q0, double* h_q1, double* h_mi, int32_t* h_S0, int32_t* h_D1,
+                      int32_t* h_D0, uint64_t* sites_out);
+/* pengk_motif_scan for first-order models.  h_S0 = n_motifs x 4, h_D = n_motifs x PENGK_MAX_MOTIF_LEN x 16 int32 (row 0
+ * and the rows from h_len[m] on unused), every used entry in [-2000, 2000], 1 <= h_len[m] <= PENGK_MAX_MOTIF_LEN.  A
+ * window x_0 .. x_{w-1} whose bases are all valid scores S0[x_0] + sum over c = 1 .. w - 1 of D[c][4 x_{c-1} + x_c]; with
+ * both_strands also the same formula on y_j = 3 - x_{w-1-j}.  d_best[m * n_seq + i] = the maximum over windows and
+ * strands, PENGK_SCORE_SENTINEL without such a window.  With D[c][4a + b] = S[c][b] and S0 = S[0] the result is
+ * pengk_motif_scan's, bit for bit.  The other arguments as pengk_motif_scan.  Best scores only: sites, p-values and
+ * re-estimation under a first-order model are not provided. */
+int pengk_motif_scan_dinuc(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_valid, const int64_t* d_offs,
+                           const uint32_t* d_lens, uint64_t n_seq, int n_motifs, const int32_t* h_S0, const int32_t* h_D,
+                           const int32_t* h_len, int both_strands, int32_t* d_best);
+
 /* ---- motif pair spacing (--spacing: which pairs of found motifs occur in the same sequences more often than chance, and
  *      whether they keep a fixed distance and orientation there; SpaMo's spacing histograms and binomial test, INTEGRATION.md
  *      7g) ------------------------------------------------------------------------------------------------------------------

@@ -38,6 +38,7 @@ EXPORTS = [
     "pengk_sites_histograms", "pengk_sites_qvalues", "pengk_qvalue_threshold",
     "pengk_motif_best_sites", "pengk_centrality_histograms", "pengk_centrality_summary", "pengk_binomial_log10_sf",
     "pengk_site_profiles", "pengk_profile_refine",
+    "pengk_site_pair_profiles", "pengk_dinuc_model", "pengk_motif_scan_dinuc",
     "pengk_spacing_histograms", "pengk_spacing_summary",
 ]
 MAX_MOTIF_LEN = 64
@@ -169,6 +170,9 @@ def lib():
         L.pengk_site_profiles.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, vp, vp, vp, vp, C.c_int, vp]
         L.pengk_profile_refine.argtypes = [vp, C.c_int, C.c_int, vp, C.c_double, vp, vp, vp, C.POINTER(C.c_int32),
                                            C.POINTER(C.c_int32), C.POINTER(u64)]
+        L.pengk_site_pair_profiles.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, vp, vp, vp, vp, C.c_int, vp]
+        L.pengk_dinuc_model.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, C.c_double, vp, vp, vp, vp, vp, vp, C.POINTER(u64)]
+        L.pengk_motif_scan_dinuc.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, vp, vp, vp, C.c_int, vp]
         L.pengk_spacing_histograms.argtypes = [vp, C.c_int, vp, vp, vp, u64, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp]
         L.pengk_spacing_summary.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, u64, u64, u64, C.c_int,
                                             C.POINTER(SpacingStruct)]
@@ -322,6 +326,27 @@ def profile_refine(counts, w, flank, bg, min_ic):
                                       pwm.ctypes.data, C.byref(first), C.byref(last), C.byref(sites)))
     return {"q": q, "ic": ic, "first": first.value, "last": last.value, "pwm": pwm[:last.value - first.value].copy(),
             "sites": sites.value}
+
+
+def dinuc_model(counts1, counts2, w, flank, bg0, bg1, alpha):
+    """one motif's first-order model from its single and pair counts (pengk_dinuc_model, CPU); counts1: at least W x 5,
+    counts2: at least W x 17 uint64 rows, W = w + 2F.  A dict: q0 (W x 4 double), q1 (W x 16), mi (W), S0 (4 int32), D1 and
+    D0 (W x 16 int32, row 0 zero), sites and flank (the clamped F)"""
+    F = clamp_flank(w, flank)
+    n = w + 2 * F
+    k1 = np.ascontiguousarray(np.asarray(counts1, np.uint64).reshape(-1, 5)[:n])
+    k2 = np.ascontiguousarray(np.asarray(counts2, np.uint64).reshape(-1, 17)[:n])
+    assert len(k1) == n and len(k2) == n
+    g0 = np.ascontiguousarray(bg0, np.float32)
+    g1 = np.ascontiguousarray(bg1, np.float32).reshape(-1)
+    assert len(g0) == 4 and len(g1) == 16
+    q0, q1, mi = np.zeros((n, 4), np.float64), np.zeros((n, 16), np.float64), np.zeros(n, np.float64)
+    S0, D1, D0 = np.zeros(4, np.int32), np.zeros((n, 16), np.int32), np.zeros((n, 16), np.int32)
+    sites = C.c_uint64()
+    _check(lib().pengk_dinuc_model(k1.ctypes.data, k2.ctypes.data, w, int(flank), g0.ctypes.data, g1.ctypes.data, float(alpha),
+                                   q0.ctypes.data, q1.ctypes.data, mi.ctypes.data, S0.ctypes.data, D1.ctypes.data,
+                                   D0.ctypes.data, C.byref(sites)))
+    return {"q0": q0, "q1": q1, "mi": mi, "S0": S0, "D1": D1, "D0": D0, "sites": sites.value, "flank": F}
 
 
 def _pad_motifs(S, lens):
@@ -748,6 +773,38 @@ class Context:
         _check(lib().pengk_site_profiles(self.h, _ptr(scan[0]), _ptr(scan[1]), _ptr(scan[2]), _ptr(scan[3]), scan[4], n, _ptr(best),
                                          _ptr(site), w.ctypes.data, th.ctypes.data, int(flank), _ptr(counts)))
         return counts
+
+    # ---- first-order models (--dinuc) ---------------------------------------------------------------------------
+    def site_pair_profiles(self, scan, best, site, widths, thr, flank, counts=None, all_valid=False):
+        """device uint64 n_motifs x MAX_MOTIF_LEN x 17: the adjacent-pair counts (bin 4a + b, a the letter before; bin 16:
+        not two bases) of every column in (-F, w + F) of the best sites at or above thr, ADDED to counts (allocated
+        zeroed if None); all_valid: the validity words are not read (d_valid = NULL)"""
+        n = len(widths)
+        w = np.ascontiguousarray(widths, np.int32)
+        th = np.ascontiguousarray(thr, np.int32)
+        if counts is None:
+            counts = self.to_device(np.zeros((max(n, 1), MAX_MOTIF_LEN, 17), np.uint64))
+        _check(lib().pengk_site_pair_profiles(self.h, _ptr(scan[0]), None if all_valid else _ptr(scan[1]), _ptr(scan[2]),
+                                              _ptr(scan[3]), scan[4], n, _ptr(best), _ptr(site), w.ctypes.data, th.ctypes.data,
+                                              int(flank), _ptr(counts)))
+        return counts
+
+    def motif_scan_dinuc(self, scan, S0, D, lens, both, words=None, all_valid=False, best=None):
+        """best[m, i] of every first-order model on every sequence of `scan`; S0: n x 4, D: n x w x 16 int32 (row 0
+        unused; padded to MAX_MOTIF_LEN here)"""
+        n = len(lens)
+        S0p = np.zeros((max(n, 1), 4), np.int32)
+        Dp = np.zeros((max(n, 1), MAX_MOTIF_LEN, 16), np.int32)
+        for m in range(n):
+            S0p[m] = np.asarray(S0[m], np.int32)
+            Dp[m, :lens[m]] = np.asarray(D[m], np.int32).reshape(-1, 16)[:lens[m]]
+        ln = np.ascontiguousarray(lens, np.int32)
+        if best is None:
+            best = self.empty((max(n, 1), max(scan[4], 1)), np.int32)
+        _check(lib().pengk_motif_scan_dinuc(self.h, _ptr(words if words is not None else scan[0]),
+                                            None if all_valid else _ptr(scan[1]), _ptr(scan[2]), _ptr(scan[3]), scan[4], n,
+                                            S0p.ctypes.data, Dp.ctypes.data, ln.ctypes.data, int(both), _ptr(best)))
+        return best
 
     def em_device(self, W, n_pwm, d_pwms, counts, bg, d_state, d_change, saturation=1e4, threshold=0.08, max_iterations=10):
         _check(lib().pengk_em_device(self.h, W, n_pwm, _ptr(d_pwms), saturation, threshold, max_iterations, _ptr(counts),

@@ -11,6 +11,8 @@
 //   sites          (--sites) the scan's walk again with per-motif thresholds: a count pass, block totals
 //                  that cut the sequences into slices of bounded records, an exclusive scan of a slice's counts and an
 //                  emit pass that writes every site at its place
+//   first order    (--dinuc) the adjacent-pair counts of the best sites, the interpolated model on the
+//                  host, and the scan again with a 16-entry boundary table behind every chunk table
 #include <string.h>
 
 #include <algorithm>
@@ -960,6 +962,204 @@ __global__ __launch_bounds__(SCAN_THREADS) void motif_sites_hist_kernel(const ui
     if (hrec[t].tests) atomicAdd(&tests[mrec[t].m], hrec[t].tests);
 }
 
+// ---- first-order models (--dinuc) --------------------------------------------------------------------
+constexpr int PAIR_BINS = PENGK_MAX_MOTIF_LEN * 17;
+
+// site_profile_kernel for adjacent pairs: per motif (blockIdx.y) and column c in (-F, w + F) of its best sites, the
+// letters a at c - 1 and b at c, read on the site's strand, ADDED to counts[(m * PENGK_MAX_MOTIF_LEN + c + F) * 17 + 4a + b]
+// (bin 16: either position outside the sequence or not A/C/G/T; row 0 stays untouched).  The same wave per 64
+// sequences and the same three words per lane; the column's (is a base, base) is kept for the next column.  Per column
+// the wave ballots the two bits of a, the two bits of b, "both are bases" and "has a site"; lane l < 16 builds the mask
+// of its own bin from them, lane 16 takes the rest, and each of the 17 adds its count once to the block's LDS bins.
+__global__ __launch_bounds__(PROF_THREADS) void site_pair_profile_kernel(const uint64_t* __restrict__ words,
+                                                                         const uint32_t* __restrict__ valid,
+                                                                         const int64_t* __restrict__ offs,
+                                                                         const uint32_t* __restrict__ lens, uint64_t n_seq,
+                                                                         const int32_t* __restrict__ best,
+                                                                         const unsigned long long* __restrict__ site,
+                                                                         const int32_t* __restrict__ wtf,
+                                                                         unsigned long long* __restrict__ counts) {
+  __shared__ uint32_t bins[PAIR_BINS];
+  const int m = blockIdx.y;
+  const int32_t w = wtf[3 * m], t = wtf[3 * m + 1], F = wtf[3 * m + 2];
+  const int32_t C = w + 2 * F;  // <= PENGK_MAX_MOTIF_LEN (the host clamps F)
+  for (int k = threadIdx.x; k < PAIR_BINS; k += PROF_THREADS) bins[k] = 0;
+  __syncthreads();
+  const int32_t* B = best + (uint64_t)m * n_seq;
+  const unsigned long long* S = site + (uint64_t)m * n_seq;
+  const int lane = threadIdx.x & 63;
+  // (every lane of a wave makes the same trips: the ballots below see the whole wave)
+  for (uint64_t i0 = blockIdx.x * (uint64_t)PROF_THREADS + (threadIdx.x & ~63); i0 < n_seq;
+       i0 += (uint64_t)gridDim.x * PROF_THREADS) {
+    const uint64_t i = i0 + lane;
+    bool sel = false;
+    int64_t L = 0, p = 0;
+    int32_t strand = 0;
+    if (i < n_seq) {
+      const int32_t b = B[i];
+      L = lens[i];
+      if (b != PENGK_SCORE_SENTINEL && b >= t && L >= w) {
+        const uint64_t c = S[i];
+        p = (int64_t)(c >> 1);
+        strand = (int32_t)(c & 1);
+        sel = p <= L - w;  // (not a window of this sequence: no site)
+      }
+    }
+    const unsigned long long has = __ballot(sel);
+    if (has == 0) continue;
+    // the bases [g0, g0 + C) of the sequence that lie inside it: [a, e), in the words j0 .. j0 + 2 of the sequence
+    const int64_t g0 = p - F;
+    int64_t a = 0, e = 0, j0 = 0;
+    uint64_t W0 = 0, W1 = 0, W2 = 0;
+    uint32_t V0 = 0, V1 = 0, V2 = 0;
+    if (sel) {
+      a = g0 > 0 ? g0 : 0;
+      e = g0 + C < L ? g0 + C : L;  // a <= p < p + w <= e
+      j0 = a >> 5;
+      const int64_t j1 = (e - 1) >> 5;  // <= j0 + 2: e - a <= 64
+      const uint64_t w0 = ((uint64_t)offs[i] >> 5) + (uint64_t)j0;
+      W0 = words[w0];
+      V0 = valid ? valid[w0] : 0xFFFFFFFFu;
+      if (j0 + 1 <= j1) {
+        W1 = words[w0 + 1];
+        V1 = valid ? valid[w0 + 1] : 0xFFFFFFFFu;
+      }
+      if (j0 + 2 <= j1) {
+        W2 = words[w0 + 2];
+        V2 = valid ? valid[w0 + 2] : 0xFFFFFFFFu;
+      }
+    }
+    bool pok = false;
+    uint32_t pb = 0;
+    for (int32_t c = 0; c < C; ++c) {
+      // column c of the site: base g0 + c on +, g0 + C - 1 - c complemented on -
+      const int64_t q = g0 + (strand ? C - 1 - c : c);
+      bool ok = false;
+      uint32_t b = 0;
+      if (sel && q >= a && q < e) {
+        const int64_t j = (q >> 5) - j0;
+        const uint64_t W = j == 0 ? W0 : (j == 1 ? W1 : W2);
+        const uint32_t V = j == 0 ? V0 : (j == 1 ? V1 : V2);
+        const uint32_t r = (uint32_t)q & 31u;
+        ok = (V >> r) & 1u;
+        b = ((uint32_t)(W >> (2 * r)) & 3u) ^ (strand ? 3u : 0u);
+      }
+      if (c > 0) {
+        const unsigned long long mo = __ballot(ok && pok), a0 = __ballot(pb & 1u), a1 = __ballot(pb & 2u),
+                                 b0 = __ballot(b & 1u), b1 = __ballot(b & 2u);
+        if (lane < 17) {
+          const unsigned long long mask = lane == 16 ? has & ~mo
+                                                     : mo & (lane & 4 ? a0 : ~a0) & (lane & 8 ? a1 : ~a1) &
+                                                           (lane & 1 ? b0 : ~b0) & (lane & 2 ? b1 : ~b1);
+          const uint32_t n = (uint32_t)__popcll(mask);
+          if (n) atomicAdd(&bins[c * 17 + lane], n);
+        }
+      }
+      pok = ok;
+      pb = b;
+    }
+  }
+  __syncthreads();
+  unsigned long long* out = counts + (uint64_t)m * PAIR_BINS;
+  for (int k = 17 + threadIdx.x; k < C * 17; k += PROF_THREADS)
+    if (bins[k]) atomicAdd(&out[k], (unsigned long long)bins[k]);
+}
+
+// The first-order scan.  A motif's chunk c owns DN_STRIDE ints per strand: the 256-entry 4-mer table -- S0 (chunk 0)
+// plus every pair term whose two columns lie inside the chunk -- and behind it the 16-entry boundary table of the one
+// pair that straddles chunks c - 1 and c, indexed by bits [8c - 2, 8c + 2) of the look-ahead buffer: the last base of
+// byte c - 1 (low) and the first of byte c (chunk 0 has no such pair; its 16 entries are not read).
+constexpr int DN_STRIDE = 256 + 16;
+
+__device__ __forceinline__ uint32_t pair_of(uint32_t b0, uint32_t b1, uint32_t b2, uint32_t b3, int c) {
+  // (c >= 1 is a compile-time constant after unrolling; c = 4, 8, 12: the pair crosses a register)
+  const uint32_t hi = c < 4 ? b0 : c < 8 ? b1 : c < 12 ? b2 : b3;
+  const uint32_t lo = c <= 4 ? b0 : c <= 8 ? b1 : b2;
+  const uint32_t v = (c & 3) ? hi >> (8 * (c & 3) - 2) : __builtin_amdgcn_alignbit(hi, lo, 30);
+  return v & 15u;
+}
+
+// walk_sequence for first-order tables, a sibling (the order-0 kernels keep their code: DESIGN.md 9.5); one motif per pass
+template <bool BOTH, class Visit>
+__device__ __forceinline__ void walk_sequence_dinuc(const uint64_t* wp, const uint32_t* vp, uint32_t L, const int32_t* tab,
+                                                    const MotifRec* mrec, int nrec, Visit& v) {
+  const uint32_t nw = (L + 31u) >> 5;
+  auto ldw = [&](uint32_t j) -> uint64_t { return j < nw ? wp[j] : 0ull; };
+  auto ldv = [&](uint32_t j) -> uint32_t {
+    if (j >= nw) return 0u;
+    if (vp) return vp[j];
+    const uint32_t rem = L - 32u * j;
+    return rem >= 32u ? 0xFFFFFFFFu : ((1u << rem) - 1u);
+  };
+  for (int r = 0; r < nrec; ++r) {
+    const MotifRec mr = mrec[r];
+    const uint64_t wmask = mr.w >= 64 ? ~0ull : ((1ull << mr.w) - 1ull);
+    const int nch = mr.nch;
+    const int32_t* tf = tab + mr.off;
+    v.begin(0, r);
+    const uint32_t nwin = L >= (uint32_t)mr.w ? L - (uint32_t)mr.w + 1u : 0u;
+    const uint64_t x0 = ldw(0), x1 = ldw(1);
+    uint32_t b0 = (uint32_t)x0, b1 = (uint32_t)(x0 >> 32), b2 = (uint32_t)x1, b3 = (uint32_t)(x1 >> 32);
+    uint64_t vb = (uint64_t)ldv(0) | ((uint64_t)ldv(1) << 32);
+    for (uint32_t s = 0, j = 2; s < nwin; ++j) {
+      uint64_t fw = ldw(j);
+      uint32_t fv = ldv(j);
+      const uint32_t cnt = nwin - s < 32u ? nwin - s : 32u;
+      for (uint32_t k = 0; k < cnt; ++k) {
+        if ((vb & wmask) == wmask) {
+          int32_t sf = 0, sr = 0;
+#pragma unroll
+          for (int c = 0; c < MAX_CHUNKS; ++c) {
+            if (c < nch) {
+              const uint32_t idx = byte_of(b0, b1, b2, b3, c);
+              sf += tf[c * DN_STRIDE + idx];
+              if (BOTH) sr += tf[(nch + c) * DN_STRIDE + idx];
+              if (c > 0) {
+                const uint32_t px = pair_of(b0, b1, b2, b3, c);
+                sf += tf[c * DN_STRIDE + 256 + px];
+                if (BOTH) sr += tf[(nch + c) * DN_STRIDE + 256 + px];
+              }
+            }
+          }
+          v.window(0, s + k, sf, sr);
+        }
+        b0 = __builtin_amdgcn_alignbit(b1, b0, 2);
+        b1 = __builtin_amdgcn_alignbit(b2, b1, 2);
+        b2 = __builtin_amdgcn_alignbit(b3, b2, 2);
+        b3 = __builtin_amdgcn_alignbit((uint32_t)fw, b3, 2);
+        fw >>= 2;
+        vb = (vb >> 1) | ((uint64_t)(fv & 1u) << 63);
+        fv >>= 1;
+      }
+      s += cnt;
+    }
+    v.end(0, r);
+  }
+}
+
+template <bool BOTH>
+__global__ __launch_bounds__(SCAN_THREADS) void motif_scan_dinuc_kernel(const uint64_t* __restrict__ words,
+                                                                        const uint32_t* __restrict__ valid,
+                                                                        const int64_t* __restrict__ offs,
+                                                                        const uint32_t* __restrict__ lens, uint64_t n_seq,
+                                                                        const int32_t* __restrict__ tables,
+                                                                        const MotifRec* __restrict__ recs,
+                                                                        const GroupRec* __restrict__ groups,
+                                                                        int32_t* __restrict__ best_out) {
+  __shared__ int32_t tab[SCAN_TABLES * 256];
+  __shared__ MotifRec mrec[SCAN_MAX_MOTIFS];
+  const GroupRec g = groups[blockIdx.y];
+  for (int t = threadIdx.x; t < g.n_ints; t += SCAN_THREADS) tab[t] = tables[g.table0 + t];
+  for (int t = threadIdx.x; t < g.m1 - g.m0; t += SCAN_THREADS) mrec[t] = recs[g.m0 + t];
+  __syncthreads();
+  for (uint64_t i = blockIdx.x * (uint64_t)SCAN_THREADS + threadIdx.x; i < n_seq; i += (uint64_t)gridDim.x * SCAN_THREADS) {
+    const uint32_t L = lens[i];
+    const uint64_t w0 = (uint64_t)offs[i] >> 5;
+    BestVisit<BOTH> v{mrec, best_out, n_seq, i, {}};
+    walk_sequence_dinuc<BOTH>(words + w0, valid ? valid + w0 : nullptr, L, tab, mrec, g.m1 - g.m0, v);
+  }
+}
+
 int grid_for(pengk_ctx* ctx, uint64_t work, uint32_t per_block, uint32_t per_cu) {
   const uint64_t need = (work + per_block - 1) / per_block;
   const uint64_t cap = (uint64_t)ctx->num_cu * per_cu;
@@ -991,6 +1191,8 @@ struct StagedMotifs {
   const int32_t* thr = nullptr;  // (h_thr given: n_motifs thresholds, by motif index)
   int n_groups = 0;
 };
+int upload_staged(pengk_ctx* ctx, const std::vector<int32_t>& tables, const std::vector<MotifRec>& recs,
+                  const std::vector<GroupRec>& groups, int n_motifs, const int32_t* h_thr, StagedMotifs* out);
 
 // chunk tables, motif records and groups (greedy, in motif order) -- and h_thr when given -- staged in ctx->d_score
 int stage_motifs(pengk_ctx* ctx, int n_motifs, const int32_t* h_S, const int32_t* h_len, int strands, const int32_t* h_thr,
@@ -1029,6 +1231,12 @@ int stage_motifs(pengk_ctx* ctx, int n_motifs, const int32_t* h_S, const int32_t
           tables.push_back(v);
         }
   }
+  return upload_staged(ctx, tables, recs, groups, n_motifs, h_thr, out);
+}
+
+// tables, motif records and groups -- and h_thr when given -- into ctx->d_score
+int upload_staged(pengk_ctx* ctx, const std::vector<int32_t>& tables, const std::vector<MotifRec>& recs,
+                  const std::vector<GroupRec>& groups, int n_motifs, const int32_t* h_thr, StagedMotifs* out) {
   const size_t tb = tables.size() * sizeof(int32_t), rb = recs.size() * sizeof(MotifRec), gb = groups.size() * sizeof(GroupRec);
   const size_t hb = h_thr ? (size_t)n_motifs * sizeof(int32_t) : 0;
   int rc = ensure_scratch(ctx, &ctx->d_score, &ctx->score_bytes, tb + rb + gb + hb);
@@ -1048,6 +1256,64 @@ int stage_motifs(pengk_ctx* ctx, int n_motifs, const int32_t* h_S, const int32_t
   out->thr = hb ? (const int32_t*)(base + tb + rb + gb) : nullptr;
   out->n_groups = (int)groups.size();
   return PENGK_OK;
+}
+
+// stage_motifs for the first-order scan: DN_STRIDE ints per chunk and strand.  In window positions j the + strand has
+// the single term S0[x_0] at j = 0 and the pair terms D[j][4 x_{j-1} + x_j], j = 1 .. w - 1; the - strand, y_j = 3 -
+// x_{w-1-j}, has S0[3 - x_{w-1}] at j = w - 1 and the pair terms D[w - j][4 (3 - x_j) + (3 - x_{j-1})].  A chunk's table
+// sums the terms whose positions lie inside it (positions at or beyond w add nothing: the entries repeat over them).
+int stage_motifs_dinuc(pengk_ctx* ctx, int n_motifs, const int32_t* h_S0, const int32_t* h_D, const int32_t* h_len, int strands,
+                       StagedMotifs* out) {
+  std::vector<int32_t> tables;
+  std::vector<MotifRec> recs;
+  std::vector<GroupRec> groups;
+  for (int m = 0; m < n_motifs; ++m) {
+    const int w = h_len[m], nch = (w + 3) / 4;
+    const int need = nch * strands * DN_STRIDE;
+    if (groups.empty() || groups.back().n_ints + need > SCAN_TABLES * 256) {
+      GroupRec g;
+      g.m0 = g.m1 = (int32_t)recs.size();
+      g.table0 = (int32_t)tables.size();
+      g.n_ints = 0;
+      groups.push_back(g);
+    }
+    GroupRec& g = groups.back();
+    MotifRec r;
+    r.off = g.n_ints;
+    r.w = w;
+    r.nch = nch;
+    r.m = m;
+    recs.push_back(r);
+    g.m1 = (int32_t)recs.size();
+    g.n_ints += need;
+    const int32_t* S0 = h_S0 + (size_t)m * 4;
+    const int32_t* D = h_D + (size_t)m * PENGK_MAX_MOTIF_LEN * 16;
+    // the pair term of positions (j - 1, j) holding the bases (a, b), j = 1 .. w - 1
+    auto pair = [&](int st, int j, int a, int b) -> int32_t {
+      return st == 0 ? D[j * 16 + 4 * a + b] : D[(w - j) * 16 + 4 * (3 - b) + (3 - a)];
+    };
+    for (int st = 0; st < strands; ++st)
+      for (int c = 0; c < nch; ++c) {
+        for (int idx = 0; idx < 256; ++idx) {
+          int32_t v = 0;
+          for (int k = 0; k < 4 && 4 * c + k < w; ++k) {
+            const int j = 4 * c + k, b = (idx >> (2 * k)) & 3;
+            if (st == 0 && j == 0) v += S0[b];
+            if (st == 1 && j == w - 1) v += S0[3 - b];
+            if (k > 0) v += pair(st, j, (idx >> (2 * k - 2)) & 3, b);
+          }
+          tables.push_back(v);
+        }
+        for (int px = 0; px < 16; ++px) tables.push_back(c > 0 ? pair(st, 4 * c, px & 3, px >> 2) : 0);
+      }
+  }
+  return upload_staged(ctx, tables, recs, groups, n_motifs, nullptr, out);
+}
+
+// clamp(lround(100 log2(p / g)), -2000, 2000) in double: log_odds of host/motif_score.cpp
+int32_t dinuc_log_odds(double p, double g) {
+  const double v = 100.0 * std::log2(p / g);
+  return (int32_t)std::lround(std::max(-2000.0, std::min(2000.0, v)));
 }
 
 // Lentz's continued fraction of the regularised incomplete beta: I_x(a, b) = x^a (1-x)^b / (a B(a, b)) * betacf(a, b, x),
@@ -1824,15 +2090,16 @@ int pengk_spacing_summary(const uint64_t* h_gaps, const uint64_t* h_lengths, uin
   return PENGK_OK;
 }
 
-int pengk_site_profiles(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_valid, const int64_t* d_offs,
-                        const uint32_t* d_lens, uint64_t n_seq, int n_motifs, const int32_t* d_best, const uint64_t* d_site,
-                        const int32_t* h_len, const int32_t* h_thr, int flank, uint64_t* d_counts) {
+// pengk_site_profiles and (pairs) pengk_site_pair_profiles: the same arguments, checks, clamp and grid
+static int site_profiles(const char* who, bool pairs, pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_valid,
+                         const int64_t* d_offs, const uint32_t* d_lens, uint64_t n_seq, int n_motifs, const int32_t* d_best,
+                         const uint64_t* d_site, const int32_t* h_len, const int32_t* h_thr, int flank, uint64_t* d_counts) {
   if (!ctx || n_motifs < 0 || flank < 0 || (n_motifs && (!h_len || !h_thr || !d_counts)) ||
       (n_seq && n_motifs && (!d_words || !d_offs || !d_lens || !d_best || !d_site)))
-    return fail(PENGK_ERR_ARG, "pengk_site_profiles: bad argument");
+    return fail(PENGK_ERR_ARG, "%s: bad argument", who);
   for (int m = 0; m < n_motifs; ++m)
     if (h_len[m] < 1 || h_len[m] > PENGK_MAX_MOTIF_LEN)
-      return fail(PENGK_ERR_ARG, "pengk_site_profiles: motif %d has width %d (1..%d)", m, h_len[m], PENGK_MAX_MOTIF_LEN);
+      return fail(PENGK_ERR_ARG, "%s: motif %d has width %d (1..%d)", who, m, h_len[m], PENGK_MAX_MOTIF_LEN);
   SCORE_ENTER(ctx);
   if (n_seq == 0 || n_motifs == 0) return PENGK_OK;
   std::vector<int32_t> wtf(3 * (size_t)n_motifs);
@@ -1850,10 +2117,18 @@ int pengk_site_profiles(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t*
   const uint64_t fill = (uint64_t)ctx->num_cu * 8 / (uint64_t)n_motifs + 1;
   const uint64_t per_motif = std::max<uint64_t>(std::min(need, fill), (n_seq >> 31) + 1);
   const dim3 grid((unsigned)per_motif, (unsigned)n_motifs);
-  hipLaunchKernelGGL(site_profile_kernel, grid, dim3(PROF_THREADS), 0, ctx->stream, d_words, d_valid, d_offs, d_lens, n_seq,
-                     d_best, (const unsigned long long*)d_site, (const int32_t*)ctx->d_misc, (unsigned long long*)d_counts);
+  hipLaunchKernelGGL(pairs ? site_pair_profile_kernel : site_profile_kernel, grid, dim3(PROF_THREADS), 0, ctx->stream, d_words,
+                     d_valid, d_offs, d_lens, n_seq, d_best, (const unsigned long long*)d_site, (const int32_t*)ctx->d_misc,
+                     (unsigned long long*)d_counts);
   PENGK_HIP(hipGetLastError());
   return PENGK_OK;
+}
+
+int pengk_site_profiles(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_valid, const int64_t* d_offs,
+                        const uint32_t* d_lens, uint64_t n_seq, int n_motifs, const int32_t* d_best, const uint64_t* d_site,
+                        const int32_t* h_len, const int32_t* h_thr, int flank, uint64_t* d_counts) {
+  return site_profiles("pengk_site_profiles", false, ctx, d_words, d_valid, d_offs, d_lens, n_seq, n_motifs, d_best, d_site, h_len,
+                       h_thr, flank, d_counts);
 }
 
 int pengk_profile_refine(const uint64_t* h_counts, int w, int flank, const float* h_bg, double min_ic, double* h_q,
@@ -1894,6 +2169,103 @@ int pengk_profile_refine(const uint64_t* h_counts, int w, int flank, const float
     const uint64_t* k = h_counts + (size_t)F * 5;
     *sites_out = k[0] + k[1] + k[2] + k[3] + k[4];
   }
+  return PENGK_OK;
+}
+
+int pengk_site_pair_profiles(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_valid, const int64_t* d_offs,
+                             const uint32_t* d_lens, uint64_t n_seq, int n_motifs, const int32_t* d_best, const uint64_t* d_site,
+                             const int32_t* h_len, const int32_t* h_thr, int flank, uint64_t* d_counts) {
+  return site_profiles("pengk_site_pair_profiles", true, ctx, d_words, d_valid, d_offs, d_lens, n_seq, n_motifs, d_best, d_site,
+                       h_len, h_thr, flank, d_counts);
+}
+
+int pengk_dinuc_model(const uint64_t* h_counts1, const uint64_t* h_counts2, int w, int flank, const float* h_bg0,
+                      const float* h_bg1, double alpha, double* h_q0, double* h_q1, double* h_mi, int32_t* h_S0, int32_t* h_D1,
+                      int32_t* h_D0, uint64_t* sites_out) {
+  if (!h_counts1 || !h_counts2 || !h_bg0 || !h_bg1 || w < 1 || w > PENGK_MAX_MOTIF_LEN || flank < 0 || !(alpha > 0.0) ||
+      !(alpha <= 1.7976931348623157e308))
+    return fail(PENGK_ERR_ARG, "pengk_dinuc_model: bad argument");
+  for (int b = 0; b < 4; ++b)
+    if (!(h_bg0[b] > 0.0f)) return fail(PENGK_ERR_ARG, "pengk_dinuc_model: background frequency %d is not positive", b);
+  for (int b = 0; b < 16; ++b)
+    if (!(h_bg1[b] > 0.0f)) return fail(PENGK_ERR_ARG, "pengk_dinuc_model: background conditional %d is not positive", b);
+  const int F = std::min(flank, (PENGK_MAX_MOTIF_LEN - w) / 2), C = w + 2 * F;
+  double g0[4], g1[16];
+  for (int b = 0; b < 4; ++b) g0[b] = (double)h_bg0[b];
+  for (int b = 0; b < 16; ++b) g1[b] = (double)h_bg1[b];
+  for (int c = 0; c < C; ++c) {
+    const uint64_t* k1 = h_counts1 + (size_t)c * 5;
+    const uint64_t* k2 = h_counts2 + (size_t)c * 17;
+    const uint64_t n1 = ((k1[0] + k1[1]) + k1[2]) + k1[3];
+    double q0[4];
+    for (int b = 0; b < 4; ++b) q0[b] = ((double)k1[b] + g0[b]) / ((double)n1 + 1.0);
+    if (h_q0)
+      for (int b = 0; b < 4; ++b) h_q0[(size_t)c * 4 + b] = q0[b];
+    if (c == 0 && h_S0)
+      for (int b = 0; b < 4; ++b) h_S0[b] = dinuc_log_odds(q0[b], g0[b]);
+    uint64_t row[4], col[4];
+    for (int a = 0; a < 4; ++a) row[a] = ((k2[4 * a] + k2[4 * a + 1]) + k2[4 * a + 2]) + k2[4 * a + 3];
+    for (int b = 0; b < 4; ++b) col[b] = ((k2[b] + k2[4 + b]) + k2[8 + b]) + k2[12 + b];
+    for (int a = 0; a < 4; ++a)
+      for (int b = 0; b < 4; ++b) {
+        const int x = 4 * a + b;
+        const double q1 = c == 0 ? q0[b] : ((double)k2[x] + alpha * q0[b]) / ((double)row[a] + alpha);
+        if (h_q1) h_q1[(size_t)c * 16 + x] = q1;
+        if (h_D1) h_D1[(size_t)c * 16 + x] = c == 0 ? 0 : dinuc_log_odds(q1, g1[x]);
+        if (h_D0) h_D0[(size_t)c * 16 + x] = c == 0 ? 0 : dinuc_log_odds(q0[b], g1[x]);
+      }
+    if (h_mi) {
+      double mi = 0.0;
+      const uint64_t N = ((row[0] + row[1]) + row[2]) + row[3];
+      if (c > 0 && N > 0)
+        for (int a = 0; a < 4; ++a)
+          for (int b = 0; b < 4; ++b) {
+            const uint64_t k = k2[4 * a + b];
+            if (k == 0) continue;
+            const double num = (double)k * (double)N, den = (double)row[a] * (double)col[b];
+            mi += ((double)k / (double)N) * std::log2(num / den);
+          }
+      h_mi[c] = mi;
+    }
+  }
+  if (sites_out) {
+    const uint64_t* k = h_counts1 + (size_t)F * 5;
+    *sites_out = k[0] + k[1] + k[2] + k[3] + k[4];
+  }
+  return PENGK_OK;
+}
+
+int pengk_motif_scan_dinuc(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_valid, const int64_t* d_offs,
+                           const uint32_t* d_lens, uint64_t n_seq, int n_motifs, const int32_t* h_S0, const int32_t* h_D,
+                           const int32_t* h_len, int both_strands, int32_t* d_best) {
+  if (!ctx || n_motifs < 0 || (n_motifs && (!h_S0 || !h_D || !h_len)) ||
+      (n_seq && n_motifs && (!d_words || !d_offs || !d_lens || !d_best)))
+    return fail(PENGK_ERR_ARG, "pengk_motif_scan_dinuc: bad argument");
+  for (int m = 0; m < n_motifs; ++m) {
+    if (h_len[m] < 1 || h_len[m] > PENGK_MAX_MOTIF_LEN)
+      return fail(PENGK_ERR_ARG, "pengk_motif_scan_dinuc: motif %d has width %d (1..%d)", m, h_len[m], PENGK_MAX_MOTIF_LEN);
+    for (int j = 0; j < 4; ++j) {
+      const int32_t v = h_S0[(size_t)m * 4 + j];
+      if (v < -2000 || v > 2000) return fail(PENGK_ERR_ARG, "pengk_motif_scan_dinuc: motif %d: log-odds %d outside [-2000, 2000]", m, v);
+    }
+    for (int j = 16; j < h_len[m] * 16; ++j) {
+      const int32_t v = h_D[(size_t)m * PENGK_MAX_MOTIF_LEN * 16 + j];
+      if (v < -2000 || v > 2000) return fail(PENGK_ERR_ARG, "pengk_motif_scan_dinuc: motif %d: log-odds %d outside [-2000, 2000]", m, v);
+    }
+  }
+  SCORE_ENTER(ctx);
+  if (n_seq == 0 || n_motifs == 0) return PENGK_OK;
+  StagedMotifs st;
+  int rc = stage_motifs_dinuc(ctx, n_motifs, h_S0, h_D, h_len, both_strands ? 2 : 1, &st);
+  if (rc) return rc;
+  const dim3 grid(grid_for(ctx, n_seq, SCAN_THREADS, 8), (unsigned)st.n_groups);
+  if (both_strands)
+    hipLaunchKernelGGL(motif_scan_dinuc_kernel<true>, grid, dim3(SCAN_THREADS), 0, ctx->stream, d_words, d_valid, d_offs, d_lens,
+                       n_seq, st.tables, st.recs, st.groups, d_best);
+  else
+    hipLaunchKernelGGL(motif_scan_dinuc_kernel<false>, grid, dim3(SCAN_THREADS), 0, ctx->stream, d_words, d_valid, d_offs, d_lens,
+                       n_seq, st.tables, st.recs, st.groups, d_best);
+  PENGK_HIP(hipGetLastError());
   return PENGK_OK;
 }
 

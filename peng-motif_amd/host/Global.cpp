@@ -56,6 +56,11 @@ double Global::refinePvalue = 1e-4;
 int Global::refineFlank = 8;
 int Global::refineIterations = 3;
 double Global::refineMinIC = 0.25;
+char* Global::dinucFilename = nullptr;
+char* Global::dinucModelsFilename = nullptr;
+double Global::dinucPvalue = 1e-4;
+int Global::dinucFlank = 0;
+double Global::dinucAlpha = 20.0;
 char* Global::spacingFilename = nullptr;
 double Global::spacingPvalue = 1e-4;
 int Global::spacingMaxGap = 150;
@@ -66,8 +71,10 @@ void Global::init(int nargs, char* args[]) {
   Alphabet::init(alphabetType);
   pengk_host::start_context();  // the device runtime starts while the FASTA files are read
   pengk_host::start_sharded_ingest();  // multi-GPU run: every rank reads its own byte range of the files
-  // (the scoring, the sites, the centrality, the refinement and the spacing scan the input after the motifs are found)
-  pengk_host::keep_host_codes(scoreMotifs || sitesFilename || centralityFilename || refineFilename || spacingFilename);
+  // (the scoring, the sites, the centrality, the refinement, the spacing and the first-order models scan the input after
+  // the motifs are found)
+  pengk_host::keep_host_codes(scoreMotifs || sitesFilename || centralityFilename || refineFilename || spacingFilename ||
+                              dinucFilename);
   // both strands are handled inside the count; sequences are always read single stranded
   // ... and every chunk of the input set is packed and sent to the device while the rest is still being read
   pengk_host::begin_streaming_pack(patternLength);
@@ -283,6 +290,38 @@ void Global::readArguments(int nargs, char* args[]) {
         log_line("ERROR", "--refine-min-ic must be a number of bits in [0, 2]");
         exit(4);
       }
+    } else if (!strcmp(a, "--dinuc")) {
+      dinucFilename = (char*)need(i, nargs, args, printHelp);
+    } else if (!strcmp(a, "--dinuc-models")) {
+      dinucModelsFilename = (char*)need(i, nargs, args, printHelp);
+    } else if (!strcmp(a, "--dinuc-pvalue")) {
+      const char* v = need(i, nargs, args, printHelp);
+      char* end = nullptr;
+      dinucPvalue = std::strtod(v, &end);
+      if (end == v || *end || !(dinucPvalue > 0.0 && dinucPvalue <= 1.0)) {
+        printHelp();
+        log_line("ERROR", "--dinuc-pvalue must be a number in (0, 1]");
+        exit(4);
+      }
+    } else if (!strcmp(a, "--dinuc-flank")) {
+      const char* v = need(i, nargs, args, printHelp);
+      char* end = nullptr;
+      const long n = std::strtol(v, &end, 10);
+      if (end == v || *end || n < 0 || n > 1000) {
+        printHelp();
+        log_line("ERROR", "--dinuc-flank must be an integer in [0, 1000]");
+        exit(4);
+      }
+      dinucFlank = (int)n;
+    } else if (!strcmp(a, "--dinuc-alpha")) {
+      const char* v = need(i, nargs, args, printHelp);
+      char* end = nullptr;
+      dinucAlpha = std::strtod(v, &end);
+      if (end == v || *end || !(dinucAlpha > 0.0 && dinucAlpha <= 1e300)) {
+        printHelp();
+        log_line("ERROR", "--dinuc-alpha must be a number above 0");
+        exit(4);
+      }
     } else if (!strcmp(a, "--spacing")) {
       spacingFilename = (char*)need(i, nargs, args, printHelp);
     } else if (!strcmp(a, "--spacing-pvalue")) {
@@ -314,6 +353,11 @@ void Global::readArguments(int nargs, char* args[]) {
     } else {
       if (pengk_host::rank() == 0) log_line("WARNING", std::string("Ignoring unknown option ") + a);
     }
+  }
+  if (dinucModelsFilename && !dinucFilename) {
+    printHelp();
+    log_line("ERROR", "--dinuc-models requires --dinuc");
+    exit(4);
   }
 }
 
@@ -372,6 +416,13 @@ void Global::printHelp() {
   printf("  --spacing-pvalue FLOAT         p-value threshold of a best site, in (0, 1] (default 1e-4)\n");
   printf("  --spacing-max-gap INT          largest gap between two sites that gets a bin of its own, 0..1024 (default 150)\n");
   printf("  --spacing-motifs INT           only the first INT motifs take part, 2..64 (default 16)\n");
+  printf("  --dinuc FILE                   build a first-order model of every motif from its best site per sequence and\n");
+  printf("                                 report (TSV) the mutual information of adjacent columns and the AUC of the\n");
+  printf("                                 first-order against the zeroth-order model (the negatives of --score-motifs)\n");
+  printf("  --dinuc-models FILE            write the models themselves to FILE (requires --dinuc)\n");
+  printf("  --dinuc-pvalue FLOAT           p-value threshold of a best site, in (0, 1] (default 1e-4)\n");
+  printf("  --dinuc-flank INT              columns modelled on either side of a motif (default 0)\n");
+  printf("  --dinuc-alpha FLOAT            weight of the zeroth-order model in the conditionals, above 0 (default 20)\n");
   printf("  --threads INT                  accepted for compatibility\n");
   printf("  --device INT                   HIP device index (default 0)\n");
   printf("  -v INT                         verbosity\n");

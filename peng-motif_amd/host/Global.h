@@ -71,6 +71,11 @@ class Global {
   static int refineFlank;                    // --refine-flank
   static int refineIterations;               // --refine-iterations
   static double refineMinIC;                 // --refine-min-ic
+  static char* dinucFilename;                // --dinuc (new: first-order models of the motifs from their sites)
+  static char* dinucModelsFilename;          // --dinuc-models
+  static double dinucPvalue;                 // --dinuc-pvalue
+  static int dinucFlank;                     // --dinuc-flank
+  static double dinucAlpha;                  // --dinuc-alpha
   static char* spacingFilename;              // --spacing (new: co-occurrence and preferred gap of motif pairs)
   static double spacingPvalue;               // --spacing-pvalue
   static int spacingMaxGap;                  // --spacing-max-gap

@@ -15,6 +15,7 @@
 #include "iupac_pattern.h"
 #include "motif_score.h"
 #include "motif_centrality.h"
+#include "motif_dinuc.h"
 #include "motif_refine.h"
 #include "motif_spacing.h"
 #include "motif_sites.h"
@@ -106,9 +107,11 @@ int main(int nargs, char** args) {
   clock.lap("process (count, sweep, hill-climb, PWMs, EM, merging)");
   peng.filter_redundancy(Global::mergeBitfactorThreshold, result);
   std::vector<MotifScore> scores;
-  // (the scoring, the sites, the centrality, the refinement and the spacing share one scan layout of the input)
+  // (the scoring, the sites, the centrality, the refinement, the spacing and the first-order models share one scan layout
+  // of the input)
   std::unique_ptr<ScanInput> scan;
-  if (Global::scoreMotifs || Global::sitesFilename || Global::centralityFilename || Global::refineFilename || Global::spacingFilename) {
+  if (Global::scoreMotifs || Global::sitesFilename || Global::centralityFilename || Global::refineFilename ||
+      Global::spacingFilename || Global::dinucFilename) {
     scan.reset(new ScanInput);
     build_scan_input(*Global::inputSequenceSet, scan.get());
   }
@@ -133,7 +136,8 @@ int main(int nargs, char** args) {
   const std::vector<MotifScore>* sc = Global::scoreMotifs ? &scores : nullptr;
   // the MEME file's order: as it is, or as the writers sort it (the same sort of the same vector: the same order)
   std::vector<IUPACPattern*> meme_order(result);
-  if (!sc && (Global::sitesFilename || Global::centralityFilename || Global::refineFilename || Global::spacingFilename))
+  if (!sc && (Global::sitesFilename || Global::centralityFilename || Global::refineFilename || Global::spacingFilename ||
+              Global::dinucFilename))
     std::sort(meme_order.begin(), meme_order.end(), sort_IUPAC_patterns);
   if (Global::sitesFilename) {
     write_motif_sites(meme_order, *Global::inputSequenceSet, *scan, *bgModel, Global::strand == Strand::BOTH_STRANDS,
@@ -159,6 +163,18 @@ int main(int nargs, char** args) {
     write_motif_spacing(meme_order, *Global::inputSequenceSet, *scan, *bgModel, Global::strand == Strand::BOTH_STRANDS,
                         Global::spacingPvalue, Global::spacingMaxGap, Global::spacingMotifs, Global::spacingFilename);
     clock.lap("spacing");
+  }
+  if (Global::dinucFilename) {
+    DinucSettings ds;
+    ds.pvalue = Global::dinucPvalue;
+    ds.flank = Global::dinucFlank;
+    ds.alpha = Global::dinucAlpha;
+    ds.bg_order = Global::bgModelOrder;
+    ds.seed = Global::scoreSeed;
+    ds.shuffled = Global::scoreNegativesShuffled;
+    write_motif_dinuc(meme_order, *Global::inputSequenceSet, *scan, *bgModel, Global::strand == Strand::BOTH_STRANDS, ds,
+                      Global::dinucFilename, Global::dinucModelsFilename ? Global::dinucModelsFilename : "");
+    clock.lap("dinuc");
   }
   scan.reset();
   if (pengk_host::rank() == 0) {

@@ -85,6 +85,36 @@ void build_scan_input(SequenceSet& set, ScanInput* in) {
   lap("uploaded");
 }
 
+void build_negatives(SequenceSet& set, const ScanInput& in, BackgroundModel& bg, int K, uint64_t seed, bool shuffled,
+                     Negatives* out) {
+  using pengk_host::check;
+  pengk_ctx* ctx = pengk_host::context();
+  const size_t n_local = in.n_local;
+  out->shuffled = shuffled;
+  out->d_words.resize(in.n_words);
+  if (shuffled) {
+    out->d_valid.resize(in.n_words);  // (a shuffle carries the sequence's other letters along)
+    check(pengk_shuffle_sequences(ctx, seed, set.getLocalBase(), n_local, in.d_words.get(), in.d_valid.get(), in.d_offs.get(),
+                                  in.d_lens.get(), out->d_words.get(), out->d_valid.get()),
+          "pengk_shuffle_sequences");
+    return;
+  }
+  // sampling thresholds of the contexts of orders 0..K
+  std::vector<uint32_t> thr;
+  for (int k = 0; k <= K; ++k)
+    for (int ctx = 0; ctx < (1 << (2 * k)); ++ctx) {
+      double c = 0.0;
+      for (int b = 0; b < 3; ++b) {
+        c += (double)bg.getV()[k][ctx * 4 + b];
+        const double t = std::floor(c * 4294967296.0);
+        thr.push_back(t >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)t);
+      }
+    }
+  check(pengk_sample_background(ctx, seed, set.getLocalBase(), n_local, in.d_offs.get(), in.d_lens.get(), K, thr.data(),
+                                out->d_words.get()),
+        "pengk_sample_background");
+}
+
 std::vector<MotifScore> score_motifs(const std::vector<IUPACPattern*>& pats, SequenceSet& set, const ScanInput& in,
                                      BackgroundModel& bg, int K, bool both_strands, uint64_t seed, bool shuffled) {
   using pengk_host::check;
@@ -93,15 +123,9 @@ std::vector<MotifScore> score_motifs(const std::vector<IUPACPattern*>& pats, Seq
   const int n_motifs = (int)pats.size();
   std::vector<MotifScore> out(n_motifs);
   const size_t n_local = in.n_local;
-  const uint64_t n_words = in.n_words;
-  DeviceBuffer<uint64_t> d_neg(n_words);
-  DeviceBuffer<uint32_t> d_neg_valid;  // (a shuffle carries the sequence's other letters along)
-  if (shuffled) {
-    d_neg_valid.resize(n_words);
-    // (the sampled path stays silent, as it was)
-    if (pengk_host::rank() == 0)
-      std::cerr << "score: negatives are dinucleotide-preserving shuffles of the input sequences (seed " << seed << ")" << std::endl;
-  }
+  // (the sampled path stays silent, as it was)
+  if (shuffled && pengk_host::rank() == 0)
+    std::cerr << "score: negatives are dinucleotide-preserving shuffles of the input sequences (seed " << seed << ")" << std::endl;
 
   // log-odds against the background letter frequencies, score ranges, histogram offsets
   const float* bg0 = bg.getV()[0];
@@ -116,18 +140,6 @@ std::vector<MotifScore> score_motifs(const std::vector<IUPACPattern*>& pats, Seq
     }
     hoffs[m + 1] = hoffs[m] + (uint64_t)(hi[m] - lo[m] + 2);
   }
-  // sampling thresholds of the contexts of orders 0..K
-  std::vector<uint32_t> thr;
-  for (int k = 0; k <= K; ++k)
-    for (int ctx = 0; ctx < (1 << (2 * k)); ++ctx) {
-      double c = 0.0;
-      for (int b = 0; b < 3; ++b) {
-        c += (double)bg.getV()[k][ctx * 4 + b];
-        const double t = std::floor(c * 4294967296.0);
-        thr.push_back(t >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)t);
-      }
-    }
-
   const uint64_t nh = std::max<uint64_t>(hoffs[n_motifs], 1);
   DeviceBuffer<uint64_t> d_hist(2 * nh);
   DeviceBuffer<int32_t> d_best((size_t)std::max(n_motifs, 1) * std::max<size_t>(n_local, 1));
@@ -139,14 +151,9 @@ std::vector<MotifScore> score_motifs(const std::vector<IUPACPattern*>& pats, Seq
         "pengk_motif_scan");
   check(pengk_score_histograms(ctx, n_motifs, d_best.get(), n_local, lo.data(), hi.data(), hoffs.data(), d_hist.get()),
         "pengk_score_histograms");
-  if (shuffled)
-    check(pengk_shuffle_sequences(ctx, seed, set.getLocalBase(), n_local, in.d_words.get(), in.d_valid.get(), in.d_offs.get(),
-                                  in.d_lens.get(), d_neg.get(), d_neg_valid.get()),
-          "pengk_shuffle_sequences");
-  else
-    check(pengk_sample_background(ctx, seed, set.getLocalBase(), n_local, in.d_offs.get(), in.d_lens.get(), K, thr.data(), d_neg.get()),
-          "pengk_sample_background");
-  check(pengk_motif_scan(ctx, d_neg.get(), shuffled ? d_neg_valid.get() : nullptr, in.d_offs.get(), in.d_lens.get(), n_local, n_motifs,
+  Negatives neg;
+  build_negatives(set, in, bg, K, seed, shuffled, &neg);
+  check(pengk_motif_scan(ctx, neg.d_words.get(), neg.valid_or_null(), in.d_offs.get(), in.d_lens.get(), n_local, n_motifs,
                          S.data(), len.data(), both, d_best.get()),
         "pengk_motif_scan");
   check(pengk_score_histograms(ctx, n_motifs, d_best.get(), n_local, lo.data(), hi.data(), hoffs.data(), d_hist.get() + nh),

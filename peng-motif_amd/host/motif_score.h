@@ -33,6 +33,19 @@ int32_t log_odds(float p, float b);
 void motif_log_odds(const std::vector<IUPACPattern*>& pats, const float* bg0, std::vector<int32_t>& S, std::vector<int32_t>& len,
                     const char* who);
 
+// The negatives of this rank's records, in the words layout of `in` (--score-motifs and --dinuc score against the same
+// ones): sampled from the background model of order K (V from bg) at the records' global indices, or, shuffled, every
+// sequence's own dinucleotide-preserving shuffle with validity words of its own (valid_or_null(): NULL for a sample,
+// whose bases are all valid).
+struct Negatives {
+  pengk_host::DeviceBuffer<uint64_t> d_words;
+  pengk_host::DeviceBuffer<uint32_t> d_valid;
+  bool shuffled = false;
+  const uint32_t* valid_or_null() { return shuffled ? d_valid.get() : nullptr; }
+};
+void build_negatives(SequenceSet& set, const ScanInput& in, BackgroundModel& bg, int K, uint64_t seed, bool shuffled,
+                     Negatives* out);
+
 struct MotifScore {
   double zoops_score = 0.0;  // AUC of the best window scores, input against its negatives (sampled or shuffled)
   double occur = 0.0;        // share of input sequences with a site, estimated at 1 % false positives
