@@ -643,6 +643,45 @@ int pengk_spacing_summary(const uint64_t* h_gaps /* B */, const uint64_t* h_leng
                           uint32_t max_gap, uint32_t max_len, int w_a, int w_b, int n_classes /* 2 or 4 */,
                           uint64_t n, uint64_t n_a, uint64_t n_b, int n_pairs, pengk_spacing* out);
 
+/* ---- motif comparison (--compare): found motifs against a database of known motifs.  Replaces a Tomtom run on the MEME
+ *      output (Gupta et al. 2007), with the Sandelin-Wasserman column score; the definitions below are this project's own
+ *      and the numbers are NOT Tomtom's.  tests/motif_compare_model.py restates them in numpy.
+ *
+ *      Column: a motif row p (4 doubles, any positive scale) becomes X_a = floor(4096 * p_a / s + 0.5), s = ((p_0 + p_1) +
+ *      p_2) + p_3, an int16 in [0, 4096].  The reverse complement of a motif reverses its column order and its letter order.
+ *      Column score: d = sum_a (X_a - Y_a)^2, s = max(0, 256 - (d >> 17)), an integer in [0, 256] (quantised columns have
+ *      d <= 2^25: identical columns score 256, two different pure columns 0; the clamp only meets made-up columns).
+ *      Alignments of a query (width wq) and a target (width wt): the target's orientation o is + or, with `both`, - (the
+ *      target reverse-complemented); m = min(min_overlap, wq, wt); the offset k = -(wt - m) .. wq - m is the query
+ *      coordinate of target column 0; the overlap starts at query column i0 = max(k, 0) and target column j0 = max(-k, 0)
+ *      and spans n = min(wq - i0, wt - j0) columns; S is the sum of its n column scores; n_offsets = the number of (o, k).
+ *      Null: h_i[v] = the (target, orientation, column) triples of the whole database that score v against query column
+ *      i, N their number, pmf_i = h_i / N in double; the null of the overlap [i0, i0 + n) is the convolution of its n
+ *      pmfs in double (every term non-negative), p_offset = min(1, P(sum >= S)), and exactly 1 where S does not exceed
+ *      the smallest sum the null can give (the sum over the n columns of the lowest v with h_i[v] > 0).
+ *      Best alignment of a pair: the smallest p_offset, then the larger overlap, + before -, the smaller k. */
+/* Pure CPU.  X[j * 4 + a] of the w rows of h_rows.  PENGK_ERR_ARG: w outside 1..PENGK_MAX_MOTIF_LEN, a negative or NaN
+ * entry, a row whose sum is not a positive finite number. */
+int pengk_compare_quantize(const double* h_rows /* w x 4 */, int w, int16_t* h_X /* w x 4 */);
+/* h_hist[(q * PENGK_MAX_MOTIF_LEN + i) * 257 + v] = h_i[v] of query q (rows at and above its width: zero).  Motifs are
+ * n x PENGK_MAX_MOTIF_LEN x 4 int16, only the first h_*len[i] columns are read.  Integer throughout: exact.
+ * PENGK_ERR_ARG (naming the function and the argument): n_q or n_t < 1, a width outside 1..PENGK_MAX_MOTIF_LEN, an entry
+ * outside [0, 4096].  Synchronises with the host. */
+int pengk_compare_nulls(pengk_ctx* ctx, int n_q, const int16_t* h_QX, const int32_t* h_qlen, int n_t, const int16_t* h_TX,
+                        const int32_t* h_tlen, int both, uint64_t* h_hist /* n_q x PENGK_MAX_MOTIF_LEN x 257 */);
+/* The best alignment of every (query, target): h_align[(q * n_t + t) * 5 ..] = offset, orientation (0 +, 1 -), overlap,
+ * score, n_offsets; h_p[q * n_t + t] = its p_offset.  The nulls are rebuilt on the device.  Device memory is bounded:
+ * queries go in batches of at most 256 MiB of tabulated tails (a query of width 64 needs 92 MB) and 2^22 records.
+ * Errors as pengk_compare_nulls, and PENGK_ERR_ARG for min_overlap < 1.  Synchronises with the host. */
+int pengk_compare_motifs(pengk_ctx* ctx, int n_q, const int16_t* h_QX, const int32_t* h_qlen, int n_t, const int16_t* h_TX,
+                         const int32_t* h_tlen, int both, int min_overlap, int32_t* h_align /* n_q x n_t x 5 */,
+                         double* h_p /* n_q x n_t */);
+/* Pure CPU, one query's n_t targets: p_match = -expm1(n_offsets * log1p(-p_offset)), 1 where p_offset is 1; evalue =
+ * p_match * n_t; qvalue: Benjamini-Hochberg over the n_t targets -- in ascending p_match (database order on ties) q_(r) =
+ * min over r' >= r of p_(r') * n_t / r', at most 1. */
+int pengk_compare_summary(const double* h_p /* n_t */, const int32_t* h_noff /* n_t */, int n_t, double* h_p_match,
+                          double* h_evalue, double* h_qvalue);
+
 /* Self-test of the division sequence the serial EM's weights kernel uses where a PWM's operand ranges allow (the IEEE
  * division's instructions without its range scaling: csrc/em.hip, lean_div; src/peng.cpp:124-125, 186 are the three
  * divisions of a weight).  4096 x 256 threads draw pairs_per_thread random operand pairs each, keep those inside the

@@ -40,6 +40,7 @@ EXPORTS = [
     "pengk_site_profiles", "pengk_profile_refine",
     "pengk_site_pair_profiles", "pengk_dinuc_model", "pengk_motif_scan_dinuc",
     "pengk_spacing_histograms", "pengk_spacing_summary",
+    "pengk_compare_quantize", "pengk_compare_nulls", "pengk_compare_motifs", "pengk_compare_summary",
 ]
 MAX_MOTIF_LEN = 64
 SCORE_SENTINEL = -2 ** 31
@@ -48,6 +49,7 @@ SITE = np.dtype([("seq", np.uint32), ("pos", np.uint32), ("score", np.int32), ("
 CENTRALITY_MAX_LEN = 65536
 SPACING_MAX_MOTIFS = 64
 SPACING_MAX_GAP = 1024
+COMPARE_BINS = 257
 SPACING_CLASSES = ("same_downstream", "same_upstream", "opposite_downstream", "opposite_upstream")
 
 
@@ -176,6 +178,10 @@ def lib():
         L.pengk_spacing_histograms.argtypes = [vp, C.c_int, vp, vp, vp, u64, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp]
         L.pengk_spacing_summary.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, u64, u64, u64, C.c_int,
                                             C.POINTER(SpacingStruct)]
+        L.pengk_compare_quantize.argtypes = [vp, C.c_int, vp]
+        L.pengk_compare_nulls.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, vp]
+        L.pengk_compare_motifs.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp]
+        L.pengk_compare_summary.argtypes = [vp, vp, C.c_int, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -347,6 +353,40 @@ def dinuc_model(counts1, counts2, w, flank, bg0, bg1, alpha):
                                    q0.ctypes.data, q1.ctypes.data, mi.ctypes.data, S0.ctypes.data, D1.ctypes.data,
                                    D0.ctypes.data, C.byref(sites)))
     return {"q0": q0, "q1": q1, "mi": mi, "S0": S0, "D1": D1, "D0": D0, "sites": sites.value, "flank": F}
+
+
+def compare_quantize(rows):
+    """the quantised columns (w x 4 int16 in [0, 4096]) of a motif's rows (w x 4, any positive scale;
+    pengk_compare_quantize, CPU)"""
+    r = np.ascontiguousarray(rows, np.float64).reshape(-1, 4)
+    X = np.zeros((len(r), 4), np.int16)
+    _check(lib().pengk_compare_quantize(r.ctypes.data, len(r), X.ctypes.data))
+    return X
+
+
+def compare_summary(p_offset, n_offsets):
+    """(p_match, evalue, qvalue) of one query's targets from their p_offset and n_offsets (pengk_compare_summary, CPU)"""
+    p = np.ascontiguousarray(p_offset, np.float64)
+    n = np.ascontiguousarray(n_offsets, np.int32)
+    assert p.shape == n.shape
+    pm, ev, q = (np.zeros(len(p), np.float64) for _ in range(3))
+    _check(lib().pengk_compare_summary(p.ctypes.data, n.ctypes.data, len(p), pm.ctypes.data, ev.ctypes.data, q.ctypes.data))
+    return pm, ev, q
+
+
+def _pad_columns(motifs, lens=None):
+    """a list of (w x 4) integer motifs as (n x MAX_MOTIF_LEN x 4 int16, widths); lens: widths to pass instead of the
+    arrays' own (the argument checks)"""
+    n = len(motifs)
+    X = np.zeros((max(n, 1), MAX_MOTIF_LEN, 4), np.int16)
+    ln = np.zeros(max(n, 1), np.int32)
+    for m in range(n):
+        x = np.asarray(motifs[m]).reshape(-1, 4)
+        ln[m] = len(x)
+        X[m, :min(len(x), MAX_MOTIF_LEN)] = x[:MAX_MOTIF_LEN]
+    if lens is not None:
+        ln[:n] = lens
+    return X, ln
 
 
 def _pad_motifs(S, lens):
@@ -805,6 +845,28 @@ class Context:
                                             None if all_valid else _ptr(scan[1]), _ptr(scan[2]), _ptr(scan[3]), scan[4], n,
                                             S0p.ctypes.data, Dp.ctypes.data, ln.ctypes.data, int(both), _ptr(best)))
         return best
+
+    # ---- motif comparison (--compare) --------------------------------------------------------------------------
+    def compare_nulls(self, queries, targets, both, qlens=None, tlens=None):
+        """the null histograms (n_q x MAX_MOTIF_LEN x 257 uint64) of quantised queries against a database of quantised
+        targets (lists of w x 4 integer arrays; pengk_compare_nulls)"""
+        QX, ql = _pad_columns(queries, qlens)
+        TX, tl = _pad_columns(targets, tlens)
+        hist = np.zeros((max(len(queries), 1), MAX_MOTIF_LEN, COMPARE_BINS), np.uint64)
+        _check(lib().pengk_compare_nulls(self.h, len(queries), QX.ctypes.data, ql.ctypes.data, len(targets), TX.ctypes.data,
+                                         tl.ctypes.data, int(both), hist.ctypes.data))
+        return hist
+
+    def compare_motifs(self, queries, targets, both, min_overlap=5, qlens=None, tlens=None):
+        """(align, p): the best alignment of every (query, target) -- align (n_q x n_t x 5 int32: offset, orientation,
+        overlap, score, n_offsets) and its p_offset (n_q x n_t double; pengk_compare_motifs)"""
+        QX, ql = _pad_columns(queries, qlens)
+        TX, tl = _pad_columns(targets, tlens)
+        align = np.zeros((max(len(queries), 1), max(len(targets), 1), 5), np.int32)
+        p = np.zeros((max(len(queries), 1), max(len(targets), 1)), np.float64)
+        _check(lib().pengk_compare_motifs(self.h, len(queries), QX.ctypes.data, ql.ctypes.data, len(targets), TX.ctypes.data,
+                                          tl.ctypes.data, int(both), int(min_overlap), align.ctypes.data, p.ctypes.data))
+        return align, p
 
     def em_device(self, W, n_pwm, d_pwms, counts, bg, d_state, d_change, saturation=1e4, threshold=0.08, max_iterations=10):
         _check(lib().pengk_em_device(self.h, W, n_pwm, _ptr(d_pwms), saturation, threshold, max_iterations, _ptr(counts),

@@ -48,6 +48,7 @@ static int warm_code_objects() {
   if (!rc) rc = warm_iupac();
   if (!rc) rc = warm_em();
   if (!rc) rc = warm_similarity();
+  if (!rc) rc = warm_compare();
   return rc;
 }
 
@@ -150,6 +151,7 @@ int pengk_destroy(pengk_ctx* ctx) {
   if (ctx->d_bg_partials) (void)hipFree(ctx->d_bg_partials);
   if (ctx->d_count_aux) (void)hipFree(ctx->d_count_aux);
   if (ctx->d_sim) (void)hipFree(ctx->d_sim);
+  if (ctx->d_cmp) (void)hipFree(ctx->d_cmp);
   if (ctx->d_score) (void)hipFree(ctx->d_score);
   if (ctx->d_sites) (void)hipFree(ctx->d_sites);
   if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);

@@ -73,6 +73,8 @@ struct pengk_ctx {
   int scatter_blocks_per_cu = 0; // tuning hook: workgroups per CU of the partitioned scan (0 = default)
   void* d_sim = nullptr;         // motif similarity grid: PWMs | complements | lengths | sites | scores
   size_t sim_bytes = 0;
+  void* d_cmp = nullptr;         // motif comparison: motifs | database columns | null histograms | tails | records (compare.hip)
+  size_t cmp_bytes = 0;
   void* d_score = nullptr;       // motif scoring: chunk tables | motif records | group records (score.hip)
   size_t score_bytes = 0;
   void* d_sites = nullptr;       // motif sites: per-sequence | per-block | per-motif totals, or a slice's record offsets | tile sums
@@ -95,6 +97,7 @@ int count_init_device();        // per-device kernel attributes of count.hip (cu
 int warm_stats();
 int warm_iupac();
 int warm_similarity();
+int warm_compare();
 int warm_em();  // (one kernel of each translation unit: its code object is loaded)
 void comm_release(pengk_ctx* ctx);  // destroys the RCCL communicator, if any
 

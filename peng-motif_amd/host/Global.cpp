@@ -61,6 +61,11 @@ char* Global::dinucModelsFilename = nullptr;
 double Global::dinucPvalue = 1e-4;
 int Global::dinucFlank = 0;
 double Global::dinucAlpha = 20.0;
+char* Global::compareFilename = nullptr;
+char* Global::compareDbFilename = nullptr;
+double Global::compareEvalue = 1.0;
+int Global::compareMinOverlap = 5;
+std::vector<MemeMotif> Global::compareDb;
 char* Global::spacingFilename = nullptr;
 double Global::spacingPvalue = 1e-4;
 int Global::spacingMaxGap = 150;
@@ -68,6 +73,7 @@ int Global::spacingMotifs = 16;
 
 void Global::init(int nargs, char* args[]) {
   readArguments(nargs, args);
+  readCompareDb();  // (a database that cannot be used ends the run before the input is read)
   Alphabet::init(alphabetType);
   pengk_host::start_context();  // the device runtime starts while the FASTA files are read
   pengk_host::start_sharded_ingest();  // multi-GPU run: every rank reads its own byte range of the files
@@ -121,6 +127,15 @@ const char* need(int& i, int nargs, char* args[], void (*help)()) {
   return args[i];
 }
 }  // namespace
+
+void Global::readCompareDb() {
+  if (!compareDbFilename) return;
+  std::string err;
+  if (!read_meme_db(compareDbFilename, PENGK_MAX_MOTIF_LEN, &compareDb, &err)) {
+    if (pengk_host::rank() == 0) log_line("ERROR", "--compare-db: " + err);
+    exit(4);
+  }
+}
 
 void Global::readArguments(int nargs, char* args[]) {
   if (nargs > 1 && !strcmp(args[1], "-h")) {
@@ -322,6 +337,29 @@ void Global::readArguments(int nargs, char* args[]) {
         log_line("ERROR", "--dinuc-alpha must be a number above 0");
         exit(4);
       }
+    } else if (!strcmp(a, "--compare")) {
+      compareFilename = (char*)need(i, nargs, args, printHelp);
+    } else if (!strcmp(a, "--compare-db")) {
+      compareDbFilename = (char*)need(i, nargs, args, printHelp);
+    } else if (!strcmp(a, "--compare-evalue")) {
+      const char* v = need(i, nargs, args, printHelp);
+      char* end = nullptr;
+      compareEvalue = std::strtod(v, &end);
+      if (end == v || *end || !(compareEvalue >= 0.0 && compareEvalue <= 1e300)) {
+        printHelp();
+        log_line("ERROR", "--compare-evalue must be a number, 0 or above");
+        exit(4);
+      }
+    } else if (!strcmp(a, "--compare-min-overlap")) {
+      const char* v = need(i, nargs, args, printHelp);
+      char* end = nullptr;
+      const long n = std::strtol(v, &end, 10);
+      if (end == v || *end || n < 1 || n > PENGK_MAX_MOTIF_LEN) {
+        printHelp();
+        log_line("ERROR", "--compare-min-overlap must be an integer in [1, 64]");
+        exit(4);
+      }
+      compareMinOverlap = (int)n;
     } else if (!strcmp(a, "--spacing")) {
       spacingFilename = (char*)need(i, nargs, args, printHelp);
     } else if (!strcmp(a, "--spacing-pvalue")) {
@@ -357,6 +395,11 @@ void Global::readArguments(int nargs, char* args[]) {
   if (dinucModelsFilename && !dinucFilename) {
     printHelp();
     log_line("ERROR", "--dinuc-models requires --dinuc");
+    exit(4);
+  }
+  if (!compareFilename != !compareDbFilename) {
+    printHelp();
+    log_line("ERROR", compareFilename ? "--compare requires --compare-db" : "--compare-db requires --compare");
     exit(4);
   }
 }
@@ -423,6 +466,11 @@ void Global::printHelp() {
   printf("  --dinuc-pvalue FLOAT           p-value threshold of a best site, in (0, 1] (default 1e-4)\n");
   printf("  --dinuc-flank INT              columns modelled on either side of a motif (default 0)\n");
   printf("  --dinuc-alpha FLOAT            weight of the zeroth-order model in the conditionals, above 0 (default 20)\n");
+  printf("  --compare FILE                 compare every motif with the motifs of --compare-db and write its matches (TSV:\n");
+  printf("                                 target, offset, orientation, overlap, score, p-, E- and q-value)\n");
+  printf("  --compare-db FILE              the motif database, MEME format (requires --compare, and the reverse)\n");
+  printf("  --compare-evalue FLOAT         only matches with an E-value at or below it are written (default 1)\n");
+  printf("  --compare-min-overlap INT      columns an alignment must span, 1..64 (default 5)\n");
   printf("  --threads INT                  accepted for compatibility\n");
   printf("  --device INT                   HIP device index (default 0)\n");
   printf("  -v INT                         verbosity\n");

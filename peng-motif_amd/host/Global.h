@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 
+#include "meme_db.h"
 #include "shared/SequenceSet.h"
 
 enum class Strand { PLUS_STRAND, BOTH_STRANDS };
@@ -76,6 +77,11 @@ class Global {
   static double dinucPvalue;                 // --dinuc-pvalue
   static int dinucFlank;                     // --dinuc-flank
   static double dinucAlpha;                  // --dinuc-alpha
+  static char* compareFilename;              // --compare (new: the found motifs against a MEME motif database)
+  static char* compareDbFilename;            // --compare-db
+  static double compareEvalue;               // --compare-evalue
+  static int compareMinOverlap;              // --compare-min-overlap
+  static std::vector<MemeMotif> compareDb;   // ... the database, read before the sequences are
   static char* spacingFilename;              // --spacing (new: co-occurrence and preferred gap of motif pairs)
   static double spacingPvalue;               // --spacing-pvalue
   static int spacingMaxGap;                  // --spacing-max-gap
@@ -86,6 +92,7 @@ class Global {
 
  private:
   static void readArguments(int nargs, char* args[]);
+  static void readCompareDb();
   static void printHelp();
 };
 

@@ -15,6 +15,7 @@
 #include "iupac_pattern.h"
 #include "motif_score.h"
 #include "motif_centrality.h"
+#include "motif_compare.h"
 #include "motif_dinuc.h"
 #include "motif_refine.h"
 #include "motif_spacing.h"
@@ -177,6 +178,16 @@ int main(int nargs, char** args) {
     clock.lap("dinuc");
   }
   scan.reset();
+  // (the comparison reads neither the sequences nor their scan layout: rank 0 alone runs it)
+  if (Global::compareFilename && pengk_host::rank() == 0) {
+    std::vector<IUPACPattern*> q(result);
+    if (!sc) std::sort(q.begin(), q.end(), sort_IUPAC_patterns);
+    CompareSettings cs;
+    cs.evalue = Global::compareEvalue;
+    cs.min_overlap = Global::compareMinOverlap;
+    write_motif_compare(q, Global::compareDb, Global::strand == Strand::BOTH_STRANDS, cs, Global::compareFilename);
+    clock.lap("compare");
+  }
   if (pengk_host::rank() == 0) {
     if (Global::outputFilename) peng.printShortMeme(result, Global::outputFilename, bgModel, sc);
     if (Global::jsonFilename) peng.printJson(result, Global::jsonFilename, VERSION_NUMBER, bgModel, sc);
