@@ -658,7 +658,8 @@ int pengk_spacing_summary(const uint64_t* h_gaps /* B */, const uint64_t* h_leng
  *      Null: h_i[v] = the (target, orientation, column) triples of the whole database that score v against query column
  *      i, N their number, pmf_i = h_i / N in double; the null of the overlap [i0, i0 + n) is the convolution of its n
  *      pmfs in double (every term non-negative), p_offset = min(1, P(sum >= S)), and exactly 1 where S does not exceed
- *      the smallest sum the null can give (the sum over the n columns of the lowest v with h_i[v] > 0).
+ *      the smallest sum the null can give (the sum over the n columns of the lowest v with h_i[v] > 0).  Within one
+ *      overlap p_offset never rises with S, whatever the rounding of the sums.
  *      Best alignment of a pair: the smallest p_offset, then the larger overlap, + before -, the smaller k. */
 /* Pure CPU.  X[j * 4 + a] of the w rows of h_rows.  PENGK_ERR_ARG: w outside 1..PENGK_MAX_MOTIF_LEN, a negative or NaN
  * entry, a row whose sum is not a positive finite number. */
@@ -671,7 +672,7 @@ int pengk_compare_nulls(pengk_ctx* ctx, int n_q, const int16_t* h_QX, const int3
                         const int32_t* h_tlen, int both, uint64_t* h_hist /* n_q x PENGK_MAX_MOTIF_LEN x 257 */);
 /* The best alignment of every (query, target): h_align[(q * n_t + t) * 5 ..] = offset, orientation (0 +, 1 -), overlap,
  * score, n_offsets; h_p[q * n_t + t] = its p_offset.  The nulls are rebuilt on the device.  Device memory is bounded:
- * queries go in batches of at most 256 MiB of tabulated tails (a query of width 64 needs 92 MB) and 2^22 records.
+ * queries go in batches of at most 256 MiB of tabulated tails (a query of width 64 needs 94 MB) and 2^22 records.
  * Errors as pengk_compare_nulls, and PENGK_ERR_ARG for min_overlap < 1.  Synchronises with the host. */
 int pengk_compare_motifs(pengk_ctx* ctx, int n_q, const int16_t* h_QX, const int32_t* h_qlen, int n_t, const int16_t* h_TX,
                          const int32_t* h_tlen, int both, int min_overlap, int32_t* h_align /* n_q x n_t x 5 */,
@@ -681,6 +682,15 @@ int pengk_compare_motifs(pengk_ctx* ctx, int n_q, const int16_t* h_QX, const int
  * min over r' >= r of p_(r') * n_t / r', at most 1. */
 int pengk_compare_summary(const double* h_p /* n_t */, const int32_t* h_noff /* n_t */, int n_t, double* h_p_match,
                           double* h_evalue, double* h_qvalue);
+/* Test hook: the whole tail table of ONE query of width w whose null histograms are h_hist (rows i = 0 .. w - 1, N = the
+ * sum of row 0), from the kernel, grid, block size and table layout that pengk_compare_motifs uses for a query that is a
+ * batch of its own.  h_tails, in the device's order: i0 ascending, then n = 1 .. w - i0, each with 256 n + 1 doubles
+ * tail(i0, n)[S] = the p_offset of an overlap [i0, i0 + n) with score S; (i0, n) starts at sum over i0' < i0 of
+ * L(w - i0') + L(n - 1), L(m) = 128 m (m + 1) + m, and the table holds sum over i0 of L(w - i0) doubles (w = 64:
+ * 11 716 640).  PENGK_ERR_ARG (before the device is touched): a NULL argument, w outside 1..PENGK_MAX_MOTIF_LEN, rows
+ * whose sums differ, N = 0 or N > 2^32 (the largest N a database that pengk_compare_nulls accepts can give).
+ * Synchronises with the host. */
+int pengk_test_compare_tails(pengk_ctx* ctx, int w, const uint64_t* h_hist /* w x 257 */, double* h_tails);
 
 /* Self-test of the division sequence the serial EM's weights kernel uses where a PWM's operand ranges allow (the IEEE
  * division's instructions without its range scaling: csrc/em.hip, lean_div; src/peng.cpp:124-125, 186 are the three

@@ -40,7 +40,7 @@ EXPORTS = [
     "pengk_site_profiles", "pengk_profile_refine",
     "pengk_site_pair_profiles", "pengk_dinuc_model", "pengk_motif_scan_dinuc",
     "pengk_spacing_histograms", "pengk_spacing_summary",
-    "pengk_compare_quantize", "pengk_compare_nulls", "pengk_compare_motifs", "pengk_compare_summary",
+    "pengk_compare_quantize", "pengk_compare_nulls", "pengk_compare_motifs", "pengk_compare_summary", "pengk_test_compare_tails",
 ]
 MAX_MOTIF_LEN = 64
 SCORE_SENTINEL = -2 ** 31
@@ -182,6 +182,7 @@ def lib():
         L.pengk_compare_nulls.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, vp]
         L.pengk_compare_motifs.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp]
         L.pengk_compare_summary.argtypes = [vp, vp, C.c_int, vp, vp, vp]
+        L.pengk_test_compare_tails.argtypes = [vp, C.c_int, vp, vp]
         _lib = L
     return _lib
 
@@ -362,6 +363,11 @@ def compare_quantize(rows):
     X = np.zeros((len(r), 4), np.int16)
     _check(lib().pengk_compare_quantize(r.ctypes.data, len(r), X.ctypes.data))
     return X
+
+
+def compare_tails_before(n):
+    """the doubles of tail(i0, 1) .. tail(i0, n - 1): sum over n' < n of 256 n' + 1"""
+    return 128 * (n - 1) * n + (n - 1)
 
 
 def compare_summary(p_offset, n_offsets):
@@ -867,6 +873,15 @@ class Context:
         _check(lib().pengk_compare_motifs(self.h, len(queries), QX.ctypes.data, ql.ctypes.data, len(targets), TX.ctypes.data,
                                           tl.ctypes.data, int(both), int(min_overlap), align.ctypes.data, p.ctypes.data))
         return align, p
+
+    def compare_tails(self, hist, w=None):
+        """the tail table of one query whose null histograms are hist (w x 257 counts), flat and in the device's order:
+        i0 ascending, then n = 1 .. w - i0, each with 256 n + 1 doubles (pengk_test_compare_tails)"""
+        h = np.ascontiguousarray(hist, np.uint64).reshape(-1, COMPARE_BINS)
+        w = len(h) if w is None else int(w)
+        tails = np.zeros(sum(compare_tails_before(w - i0 + 1) for i0 in range(min(max(w, 0), MAX_MOTIF_LEN))) or 1, np.float64)
+        _check(lib().pengk_test_compare_tails(self.h, w, h.ctypes.data, tails.ctypes.data))
+        return tails
 
     def em_device(self, W, n_pwm, d_pwms, counts, bg, d_state, d_change, saturation=1e4, threshold=0.08, max_iterations=10):
         _check(lib().pengk_em_device(self.h, W, n_pwm, _ptr(d_pwms), saturation, threshold, max_iterations, _ptr(counts),

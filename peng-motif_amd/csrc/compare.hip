@@ -15,14 +15,15 @@
 //   compare_tail_kernel   per (query, i0): the chain pmf_i0, pmf_i0 * pmf_i0+1, ... in fp64 (pmf_i = h_i / N), resident
 //                         in LDS (64 x 256 + 1 doubles = 128 KiB, between zeros so that no index is tested), each
 //                         thread holding up to 17 of the new values in registers; after every step the suffix sums
-//                         P(sum >= S) -- at most 1, and 1 up to the smallest sum the null can give -- go to the tail table.  All terms are non-negative:
-//                         any summation order stays within a relative n_terms * 2^-53 of the exact sum.
+//                         P(sum >= S) -- at most 1, 1 up to the smallest sum the null can give, never rising with S --
+//                         go to the tail table.  All terms are non-negative: any summation order stays within a relative
+//                         n_terms * 2^-53 of the exact sum.
 //   compare_align_kernel  per (query, tile of 64 targets), a wave per target: a lane owns an (orientation, offset), sums
 //                         the column scores of the overlap, looks its tail up and keeps the best by (smaller p, larger
 //                         overlap, + before -, smaller offset); a butterfly over the wave selects the pair's alignment.
 //
-// Device memory is bounded: a query of width w needs sum over i0, n of (256 n + 1) doubles of tails (w = 64: 11.45 M
-// doubles, 92 MB), so queries are processed in batches of at most TAIL_BUDGET bytes of tails (256 MiB) and at most
+// Device memory is bounded: a query of width w needs sum over i0, n of (256 n + 1) doubles of tails (w = 64: 11.72 M
+// doubles, 94 MB), so queries are processed in batches of at most TAIL_BUDGET bytes of tails (256 MiB) and at most
 // PAIR_BUDGET (query, target) records (2^22, 28 bytes each); a single query is a batch of its own when it exceeds either.
 #include <math.h>
 
@@ -108,6 +109,7 @@ __global__ __launch_bounds__(TAIL_THREADS) void compare_tail_kernel(const unsign
   __shared__ double cur[TAIL_PAD + TAIL_PER * TAIL_THREADS];
   __shared__ double col[BINS];
   __shared__ double part[TAIL_THREADS];
+  __shared__ double wmax[TAIL_THREADS / 64];
   __shared__ int smin;
   int vmin = 0;
   for (int e = tid; e < TAIL_PAD + TAIL_PER * TAIL_THREADS; e += TAIL_THREADS) cur[e] = 0.0;
@@ -162,13 +164,32 @@ __global__ __launch_bounds__(TAIL_THREADS) void compare_tail_kernel(const unsign
       part[tid] += add;
       __syncthreads();
     }
-    double run = tid + 1 < TAIL_THREADS ? part[tid + 1] : 0.0;
+    const double above = tid + 1 < TAIL_THREADS ? part[tid + 1] : 0.0;
+    // A tail must not rise with S.  Within a thread's chunk it cannot; across chunks the scanned sum `above` and the
+    // next thread's own additions round differently, and the tail at the top of a chunk could lie an ulp or two below
+    // the one above it.  So no tail is smaller than the largest tail of the threads above: `low` is this thread's tail at
+    // its lowest v (the additions of the loop below, in their order), `floor_` the largest `low` of the threads above --
+    // a suffix maximum over the wave, then over the waves.
+    double low = above;
+    for (int v = hi - 1; v >= lo; --v) low += cur[TAIL_PAD + v];
+    const int lane = tid & 63, wave = tid >> 6;
+    double m = low;
+    for (int off = 1; off < 64; off <<= 1) {
+      const double other = __shfl_down(m, off, 64);
+      if (lane + off < 64) m = fmax(m, other);
+    }
+    double floor_ = __shfl_down(m, 1, 64);
+    if (lane == 63) floor_ = 0.0;
+    if (lane == 0) wmax[wave] = m;
+    __syncthreads();
+    for (int x = wave + 1; x < TAIL_THREADS / 64; ++x) floor_ = fmax(floor_, wmax[x]);
+    double run = above;
     double* o = out + tails_before(n);
     for (int v = hi - 1; v >= lo; --v) {
       run += cur[TAIL_PAD + v];
-      o[v] = v <= vmin ? 1.0 : fmin(run, 1.0);
+      o[v] = v <= vmin ? 1.0 : fmin(fmax(run, floor_), 1.0);
     }
-    // (the next step writes col, then cur and part only behind a barrier that every thread reaches after these reads)
+    // (the next step writes col, then cur, part and wmax only behind a barrier that every thread reaches after these reads)
   }
 }
 
@@ -433,6 +454,51 @@ int pengk_compare_motifs(pengk_ctx* ctx, int n_q, const int16_t* h_QX, const int
     PENGK_HIP(hipMemcpyAsync(h_p + (size_t)qa * n_t, base + pl.o_p, pairs * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     PENGK_HIP(hipStreamSynchronize(ctx->stream));
   }
+  return PENGK_OK;
+}
+
+int pengk_test_compare_tails(pengk_ctx* ctx, int w, const uint64_t* h_hist, double* h_tails) {
+  if (!ctx || !h_hist || !h_tails) return fail(PENGK_ERR_ARG, "pengk_test_compare_tails: NULL argument");
+  if (w < 1 || w > MAXL) return fail(PENGK_ERR_ARG, "pengk_test_compare_tails: w = %d (1..%d)", w, MAXL);
+  uint64_t N = 0;
+  for (int i = 0; i < w; ++i) {
+    uint64_t s = 0;
+    bool over = false;
+    for (int v = 0; v < BINS; ++v) {
+      over = over || h_hist[(size_t)i * BINS + v] > ((uint64_t)1 << 32);  // (so that the sum cannot wrap)
+      s += h_hist[(size_t)i * BINS + v];
+    }
+    if (over || s > ((uint64_t)1 << 32))
+      return fail(PENGK_ERR_ARG, "pengk_test_compare_tails: h_hist: row %d sums to more than 2^32", i);
+    if (i == 0) N = s;
+    if (s != N)
+      return fail(PENGK_ERR_ARG, "pengk_test_compare_tails: h_hist: row %d sums to %llu, row 0 to %llu", i, (unsigned long long)s,
+                  (unsigned long long)N);
+  }
+  if (N == 0) return fail(PENGK_ERR_ARG, "pengk_test_compare_tails: h_hist: the rows sum to 0");
+  // one query, a batch of its own: the layout of make_plan's row for it
+  std::vector<unsigned long long> row(MAXL, 0);
+  size_t total = 0;
+  for (int i0 = 0; i0 < w; ++i0) {
+    row[i0] = total;
+    total += (size_t)tails_before(w - i0 + 1);
+  }
+  const int32_t qlen = w;
+  const size_t o_hist = 0, o_qlen = up256((size_t)MAXL * BINS * 8), o_row = up256(o_qlen + 4), o_tails = up256(o_row + (size_t)MAXL * 8);
+  int rc = enter(ctx);
+  if (!rc) rc = ensure_scratch(ctx, &ctx->d_cmp, &ctx->cmp_bytes, up256(o_tails + total * sizeof(double)));
+  if (rc) return rc;
+  char* base = (char*)ctx->d_cmp;
+  PENGK_HIP(hipMemsetAsync(base + o_hist, 0, (size_t)MAXL * BINS * 8, ctx->stream));
+  PENGK_HIP(hipMemcpyAsync(base + o_hist, h_hist, (size_t)w * BINS * 8, hipMemcpyHostToDevice, ctx->stream));
+  PENGK_HIP(hipMemcpyAsync(base + o_qlen, &qlen, 4, hipMemcpyHostToDevice, ctx->stream));
+  PENGK_HIP(hipMemcpyAsync(base + o_row, row.data(), (size_t)MAXL * 8, hipMemcpyHostToDevice, ctx->stream));
+  hipLaunchKernelGGL(compare_tail_kernel, dim3((unsigned)MAXL), dim3(TAIL_THREADS), 0, ctx->stream,
+                     (const unsigned long long*)(base + o_hist), (const int32_t*)(base + o_qlen), (double)N,
+                     (const unsigned long long*)(base + o_row), (double*)(base + o_tails));
+  PENGK_HIP(hipGetLastError());
+  PENGK_HIP(hipMemcpyAsync(h_tails, base + o_tails, total * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  PENGK_HIP(hipStreamSynchronize(ctx->stream));  // (qlen and row are read until here)
   return PENGK_OK;
 }
 
