@@ -78,7 +78,8 @@ int pengk_set_stream(pengk_ctx* ctx, void* hip_stream);
  * tightly; set it after pengk_set_sequences); "key_cap_override" (test hook) entries per bucket region of the
  * partitioned count, 0 = automatic; "sweep_pairs" 1 (default) / 0: both strands from W = 12 on, a pattern and its reverse complement evaluated once (0: one thread per pattern; same bits); "iupac_group_bytes" (test hook) scratch budget for one group of large
  * patterns in pengk_iupac_aggregate, 0 = 1 GiB; "em_fast" 2 (default) / 1 / 0, see pengk_em; "sites_record_budget" records per slice of pengk_sites_slices
- * (default 2^24, also readable through pengk_get_info).  Info: "deferred_items" (of the last pengk_count;
+ * (default 2^24, also readable through pengk_get_info); "enrich_groups_per_launch" (test hook) motif groups per launch of
+ * pengk_motif_enrich, 1 .. 65535 (default 1024, also readable through pengk_get_info).  Info: "deferred_items" (of the last pengk_count;
  * synchronises), "count_group" (the option as set), "count_group_used" (keys per group of the emitter the last count ran:
  * 64 or 128; 0 = not the one-level partition of W = 8 / 10), "count_wrapped_workgroups" (pass-B workgroups of the last
  * count whose packed 16-bit bins wrapped and that recounted their slices exactly; 0 under groups of 64; synchronises; like
@@ -444,6 +445,48 @@ int pengk_sites_histograms(pengk_ctx* ctx, const uint64_t* d_words, const uint32
                            const uint32_t* d_lens, uint64_t n_seq, int n_motifs, const int32_t* h_S, const int32_t* h_len,
                            int both_strands, const int32_t* h_thr, const int32_t* h_hi, const uint64_t* h_hist_offs,
                            uint64_t* d_hist, uint64_t* d_tests, uint64_t* d_counts);
+/* ---- database enrichment (--enrich: which motifs of a MEME database are enriched in the input against its negatives;
+ *      this project's own definitions, not SEA's or AME's: INTEGRATION.md 7k) ------------------------------------------
+ * The scan of pengk_motif_scan with the best score of a sequence kept in a register and binned where it stands: nothing
+ * of size n_motifs x n_seq is written, so a whole database fits.  Arguments as pengk_sites_histograms: motif m owns
+ * max(0, h_hi[m] - h_thr[m] + 1) uint64 bins from d_hist + h_hist_offs[m] on.  Every sequence with at least one window
+ * whose bases are all valid adds 1 to d_scored[m] (n_motifs uint64) and, if its best window-strand score b -- exactly
+ * pengk_motif_scan's value -- is >= h_thr[m], 1 to bin b - h_thr[m]; a sequence without such a window adds nothing.
+ * Both arrays are ADDED to (caller-zeroed): shards and several calls sum exactly.  d_hist may be NULL when no motif has
+ * a bin.  n_seq = 0 or n_motifs = 0 does nothing; n_seq >= 2^32 and an h_hi[m] below the sum of the column maxima of
+ * S[m] are PENGK_ERR_ARG.  n_motifs is unbounded: the motif groups are staged and launched in batches of the option
+ * "enrich_groups_per_launch" (default 1024, 1 .. 65535; a test hook like "sites_record_budget": a small test can cross
+ * the seam between two launches; also readable through pengk_get_info).  Asynchronous on the context's stream but for
+ * the staging copies. */
+int pengk_motif_enrich(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_valid, const int64_t* d_offs,
+                       const uint32_t* d_lens, uint64_t n_seq, int n_motifs, const int32_t* h_S, const int32_t* h_len,
+                       int both_strands, const int32_t* h_thr, const int32_t* h_hi, const uint64_t* h_hist_offs,
+                       uint64_t* d_hist, uint64_t* d_scored);
+/* Pure CPU.  log10 P(X >= k) for X ~ Hypergeometric(N, K marked, n drawn), K <= N, n <= N (Fisher's one-sided tail):
+ * 0.0 for k <= max(0, n + K - N), -inf for k > min(K, n).  Loader's saddle-point form of the point mass (stirlerr / bd0)
+ * at the end of the shorter tail, then the ratio recurrence away from the mode, relative to that point mass; the
+ * complement when k lies at or below the mode.  Holds for N of 4e7 with a tail near 1 and for tails far below the
+ * smallest double. */
+int pengk_hypergeom_log10_sf(uint64_t N, uint64_t K, uint64_t n, uint64_t k, double* out);
+typedef struct {
+  int32_t threshold;       /* the reported score threshold (thr + nbins when none was tried) */
+  uint32_t n_thresholds;   /* T: the thresholds tried */
+  uint64_t pos_hits;       /* a: input sequences with a best score >= threshold */
+  uint64_t neg_hits;       /* b: negatives likewise */
+  double enrichment;       /* ((a + 1) / (n_pos + 1)) / ((b + 1) / (n_neg + 1)) */
+  double log10_pvalue;     /* log10 P(X >= a), X ~ Hypergeometric(n_pos + n_neg, a + b, n_pos) */
+  double log10_adj_pvalue; /* min(0, log10_pvalue + log10 T) */
+} pengk_enrichment;
+/* Pure CPU.  One motif's enrichment test from its two histograms of pengk_motif_enrich (h_pos over the input, h_neg over
+ * the negatives, nbins bins each, bin k = score thr + k, summed over all ranks) and the scored sequences n_pos / n_neg
+ * (d_scored).  From the top bin down a(k) / b(k) are the sums of h_pos / h_neg over the bins >= k; the threshold thr + k
+ * is tried only where h_pos[k] + h_neg[k] > 0 (elsewhere it is the test of the threshold above); T counts them.  At a
+ * tried k, p(k) = P(X >= a(k)) with N = n_pos + n_neg, K = a(k) + b(k), n = n_pos (pengk_hypergeom_log10_sf).  Reported
+ * is the k with the smallest log10 p(k), the higher threshold on equality; log10_adj_pvalue is the Bonferroni correction
+ * over the T thresholds.  T = 0: threshold thr + nbins, no hits, enrichment by the same formula, both logs 0.  A sum of
+ * h_pos above n_pos or of h_neg above n_neg is PENGK_ERR_ARG. */
+int pengk_enrich_summary(const uint64_t* h_pos, const uint64_t* h_neg, uint64_t nbins, int32_t thr, uint64_t n_pos,
+                         uint64_t n_neg, pengk_enrichment* out);
 /* Pure CPU.  Benjamini-Hochberg q-values of one motif's sites from its histogram (h_hist[k]: the sites with score t + k,
  * nbins = hi - t + 1 bins, summed over all ranks), the number of tests n_tests (d_tests, summed likewise) and
  * h_tail_from_thr = tail + (t - lo) of pengk_score_tail_pvalues.  n(k) = sum over k' >= k of h_hist[k'] (uint64, from

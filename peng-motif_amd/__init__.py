@@ -36,6 +36,7 @@ EXPORTS = [
     "pengk_motif_scan", "pengk_score_histograms", "pengk_score_summary",
     "pengk_score_tail_pvalues", "pengk_score_threshold", "pengk_sites_count", "pengk_sites_slices", "pengk_sites_emit",
     "pengk_sites_histograms", "pengk_sites_qvalues", "pengk_qvalue_threshold",
+    "pengk_motif_enrich", "pengk_hypergeom_log10_sf", "pengk_enrich_summary",
     "pengk_motif_best_sites", "pengk_centrality_histograms", "pengk_centrality_summary", "pengk_binomial_log10_sf",
     "pengk_site_profiles", "pengk_profile_refine",
     "pengk_site_pair_profiles", "pengk_dinuc_model", "pengk_motif_scan_dinuc",
@@ -56,6 +57,11 @@ SPACING_CLASSES = ("same_downstream", "same_upstream", "opposite_downstream", "o
 class CentralityStruct(C.Structure):
     _fields_ = [("sites", C.c_uint64), ("max_offset", C.c_uint32), ("window", C.c_uint32), ("in_window", C.c_uint64),
                 ("expected", C.c_double), ("log10_pvalue", C.c_double), ("log10_evalue", C.c_double)]
+
+
+class EnrichmentStruct(C.Structure):
+    _fields_ = [("threshold", C.c_int32), ("n_thresholds", C.c_uint32), ("pos_hits", C.c_uint64), ("neg_hits", C.c_uint64),
+                ("enrichment", C.c_double), ("log10_pvalue", C.c_double), ("log10_adj_pvalue", C.c_double)]
 
 
 class SpacingStruct(C.Structure):
@@ -162,6 +168,9 @@ def lib():
         L.pengk_sites_count.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, vp, vp, C.c_int, vp, vp]
         L.pengk_sites_histograms.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
         L.pengk_sites_qvalues.argtypes = [vp, u64, u64, vp, vp]
+        L.pengk_motif_enrich.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp]
+        L.pengk_hypergeom_log10_sf.argtypes = [u64, u64, u64, u64, C.POINTER(C.c_double)]
+        L.pengk_enrich_summary.argtypes = [vp, vp, u64, C.c_int32, u64, u64, C.POINTER(EnrichmentStruct)]
         L.pengk_qvalue_threshold.argtypes = [vp, u64, C.c_int32, C.c_double, C.POINTER(C.c_int32)]
         L.pengk_sites_slices.argtypes = [vp, vp, u64, C.c_int, vp, u64, vp, vp, C.POINTER(u64)]
         L.pengk_sites_emit.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, vp, vp, C.c_int, vp, vp, u64, u64, vp, u64]
@@ -298,6 +307,25 @@ def binomial_log10_sf(n, k, p):
     out = C.c_double()
     _check(lib().pengk_binomial_log10_sf(int(n), int(k), float(p), C.byref(out)))
     return out.value
+
+
+def hypergeom_log10_sf(N, K, n, k):
+    """log10 P(X >= k) for X ~ Hypergeometric(N, K marked, n drawn) (pengk_hypergeom_log10_sf, CPU)"""
+    out = C.c_double()
+    _check(lib().pengk_hypergeom_log10_sf(int(N), int(K), int(n), int(k), C.byref(out)))
+    return out.value
+
+
+def enrich_summary(pos_hist, neg_hist, thr, n_pos, n_neg):
+    """one database motif's enrichment test from its input / negative histograms of Context.motif_enrich (bin k = score
+    thr + k) and the scored sequences of either set (pengk_enrich_summary, CPU): a dict with the fields of pengk_enrichment"""
+    p = np.ascontiguousarray(pos_hist, np.uint64)
+    n = np.ascontiguousarray(neg_hist, np.uint64)
+    assert p.shape == n.shape
+    out = EnrichmentStruct()
+    _check(lib().pengk_enrich_summary(p.ctypes.data if len(p) else None, n.ctypes.data if len(n) else None, len(p), int(thr),
+                                      int(n_pos), int(n_neg), C.byref(out)))
+    return {k: getattr(out, k) for k, _ in EnrichmentStruct._fields_}
 
 
 def spacing_summary(hist_gaps, hist_lengths, max_gap, max_len, w_a, w_b, n_classes, n, n_a, n_b, n_pairs):
@@ -702,6 +730,34 @@ class Context:
                                             _ptr(counts) if counts is not None else None))
         h = hist.to_host()
         return [h[int(offs[m]):int(offs[m]) + int(nb[m])].copy() for m in range(n)], tests.to_host()[:n]
+
+    def motif_enrich(self, scan, S, lens, both, thr, hi, words=None, valid=None, all_valid=False, hist=None, scored=None,
+                     offs=None, n_seq=None):
+        """(hists, scored): hists[m] (uint64, max(0, hi[m] - thr[m] + 1) bins) the sequences of `scan` by their best score
+        of motif m minus thr[m], scored[m] the sequences with a window of valid bases (pengk_motif_enrich; downloaded).
+        words / valid: other words in the layout of `scan` (negatives); all_valid: d_valid = NULL.  hist / scored: device
+        uint64 arrays to ADD to instead of fresh zeroed ones (motif m's bins from hist[offs[m]] on, default back to
+        back); what is returned is then their content after the call.  n_seq: another count than scan[4] (argument
+        tests)."""
+        n = len(lens)
+        Sp, ln = _pad_motifs(S, lens)
+        th = np.ascontiguousarray(thr, np.int32)
+        hi = np.ascontiguousarray(hi, np.int32)
+        nb = np.maximum(hi.astype(np.int64) - th.astype(np.int64) + 1, 0)
+        if offs is None:
+            offs = np.concatenate([[0], np.cumsum(nb)])[:max(n, 1)]
+        offs = np.ascontiguousarray(offs, np.uint64)
+        if hist is None:
+            hist = self.to_device(np.zeros(max(int(nb.sum()), 1), np.uint64))
+        if scored is None:
+            scored = self.to_device(np.zeros(max(n, 1), np.uint64))
+        w = words if words is not None else scan[0]
+        v = None if all_valid else _ptr(valid if valid is not None else scan[1])
+        _check(lib().pengk_motif_enrich(self.h, _ptr(w), v, _ptr(scan[2]), _ptr(scan[3]), scan[4] if n_seq is None else n_seq, n,
+                                        Sp.ctypes.data, ln.ctypes.data, int(both), th.ctypes.data, hi.ctypes.data,
+                                        offs.ctypes.data, _ptr(hist), _ptr(scored)))
+        h = hist.to_host()
+        return [h[int(offs[m]):int(offs[m]) + int(nb[m])].copy() for m in range(n)], scored.to_host()[:n]
 
     def sites_slices(self, counts, n_seq, n_motifs):
         """(bounds, records, motif_totals) of pengk_sites_slices"""

@@ -240,6 +240,11 @@ int pengk_set_option(pengk_ctx* ctx, const char* name, int64_t value) {
     ctx->sites_record_budget = (uint64_t)value;
     return PENGK_OK;
   }
+  if (strcmp(name, "enrich_groups_per_launch") == 0) {
+    if (value < 1 || value > 65535) return fail(PENGK_ERR_ARG, "enrich_groups_per_launch must be 1 .. 65535 motif groups");
+    ctx->enrich_groups_per_launch = value;
+    return PENGK_OK;
+  }
   if (strcmp(name, "scatter_blocks_per_cu") == 0) {
     if (value < 0 || value > 8) return fail(PENGK_ERR_ARG, "scatter_blocks_per_cu must be 0 (default) .. 8");
     ctx->scatter_blocks_per_cu = (int)value;
@@ -296,6 +301,10 @@ int pengk_get_info(pengk_ctx* ctx, const char* name, int64_t* value) {
   }
   if (strcmp(name, "sites_record_budget") == 0) {
     *value = (int64_t)ctx->sites_record_budget;
+    return PENGK_OK;
+  }
+  if (strcmp(name, "enrich_groups_per_launch") == 0) {
+    *value = ctx->enrich_groups_per_launch;
     return PENGK_OK;
   }
   if (strcmp(name, "num_cu") == 0) {

@@ -80,6 +80,7 @@ struct pengk_ctx {
   void* d_sites = nullptr;       // motif sites: per-sequence | per-block | per-motif totals, or a slice's record offsets | tile sums
   size_t sites_bytes = 0;
   uint64_t sites_record_budget = 1ull << 24;  // records per slice of pengk_sites_slices (a larger sequence: a slice of its own)
+  int64_t enrich_groups_per_launch = 1024;    // motif groups per launch of pengk_motif_enrich (1024 groups: 40 MiB of tables staged at most, within gridDim.y)
   void* comm = nullptr;          // RCCL communicator (comm.hip)
   int comm_transport = 0;        // PENGK_TRANSPORT_*: how the tables of a multi-rank run are exchanged
   int comm_rank = 0, comm_world = 1;

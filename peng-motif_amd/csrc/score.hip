@@ -13,6 +13,8 @@
 //                  emit pass that writes every site at its place
 //   first order    (--dinuc) the adjacent-pair counts of the best sites, the interpolated model on the
 //                  host, and the scan again with a 16-entry boundary table behind every chunk table
+//   enrichment     (--enrich) the scan with a sequence's best score kept in a register and binned where it
+//                  stands, for a whole motif database: nothing of size motifs x sequences; Fisher's exact tail on the host
 #include <string.h>
 
 #include <algorithm>
@@ -962,6 +964,99 @@ __global__ __launch_bounds__(SCAN_THREADS) void motif_sites_hist_kernel(const ui
     if (hrec[t].tests) atomicAdd(&tests[mrec[t].m], hrec[t].tests);
 }
 
+// ---- database enrichment (pengk_motif_enrich: the histograms behind --enrich) ----------------------------
+// Per motif of the group: the global bins (bin 0 = the threshold) and the lowest score with a private bin.
+struct EnrichRec {
+  unsigned long long* H;
+  int32_t thr, top;
+};
+
+// A fifth visitor: BestVisit's register maximum, binned where it stands instead of stored.  The window loop is
+// BestVisit's (a score is above PENGK_SCORE_SENTINEL, so the maximum itself says whether there was a window); per
+// (motif, sequence) the end adds the sequence to the motif's scored counter -- one 32-bit LDS add per wave: the lanes
+// that are here together are counted by a ballot, and a lane that is not counts itself the same way -- and, at or above
+// the threshold, 1 to the bin of the best score: a private 32-bit LDS bin for the top `per` scores (HistVisit's
+// arrangement), the global uint64 bin below them.
+// No private bin or counter can wrap and none is flushed inside the loop: a sequence adds at most once per motif and
+// the host refuses n_seq >= 2^32.
+template <bool BOTH>
+struct EnrichVisit {
+  const EnrichRec* erec;
+  uint32_t* priv;
+  uint32_t* scored;
+  int per;
+  int best[SCAN_PASS];
+  __device__ __forceinline__ void begin(int q, int) { best[q] = PENGK_SCORE_SENTINEL; }
+  __device__ __forceinline__ void window(int q, uint32_t, int32_t sf, int32_t sr) { best[q] = max(best[q], BOTH ? max(sf, sr) : sf); }
+  __device__ __forceinline__ void end(int q, int rr) {
+    const int32_t b = best[q];
+    const bool had = b != PENGK_SCORE_SENTINEL;
+    const unsigned long long here = __ballot(1), hm = __ballot(had);
+    if (hm && (int)__lane_id() == __ffsll((long long)here) - 1) atomicAdd(&scored[rr], (uint32_t)__popcll(hm));
+    if (!had) return;
+    const EnrichRec e = erec[rr];
+    if (b < e.thr) return;
+    if (b >= e.top) atomicAdd(&priv[rr * per + (b - e.top)], 1u);
+    else atomicAdd(&e.H[(int64_t)b - e.thr], 1ull);
+  }
+};
+
+template <bool BOTH>
+__global__ __launch_bounds__(SCAN_THREADS) void motif_enrich_kernel(const uint64_t* __restrict__ words,
+                                                                    const uint32_t* __restrict__ valid,
+                                                                    const int64_t* __restrict__ offs,
+                                                                    const uint32_t* __restrict__ lens, uint64_t n_seq,
+                                                                    const int32_t* __restrict__ tables,
+                                                                    const MotifRec* __restrict__ recs,
+                                                                    const GroupRec* __restrict__ groups,
+                                                                    const int32_t* __restrict__ thr,
+                                                                    const int32_t* __restrict__ hi,
+                                                                    const uint64_t* __restrict__ hoffs,
+                                                                    unsigned long long* __restrict__ hist,
+                                                                    unsigned long long* __restrict__ scored_out) {
+  __shared__ int32_t tab[SCAN_TABLES * 256];
+  __shared__ MotifRec mrec[SCAN_MAX_MOTIFS];
+  __shared__ EnrichRec erec[SCAN_MAX_MOTIFS];
+  __shared__ uint32_t scored[SCAN_MAX_MOTIFS];
+  __shared__ uint32_t priv[QH_PRIV_BINS];
+  const GroupRec g = groups[blockIdx.y];
+  const int nrec = g.m1 - g.m0;
+  const int per = QH_PRIV_BINS / nrec;  // (1 <= nrec <= SCAN_MAX_MOTIFS: at least 64 bins each)
+  for (int t = threadIdx.x; t < g.n_ints; t += SCAN_THREADS) tab[t] = tables[g.table0 + t];
+  for (int t = threadIdx.x; t < nrec; t += SCAN_THREADS) {
+    const MotifRec mr = recs[g.m0 + t];
+    mrec[t] = mr;
+    // the private bins: scores (hi - per, hi], none below the threshold (hi >= every score: the host checked it)
+    const int64_t tp = (int64_t)hi[mr.m] - per + 1;
+    EnrichRec e;
+    e.H = hist + hoffs[mr.m];
+    e.thr = thr[mr.m];
+    e.top = tp > (int64_t)e.thr ? (int32_t)tp : e.thr;
+    erec[t] = e;
+    scored[t] = 0;
+  }
+  for (int t = threadIdx.x; t < QH_PRIV_BINS; t += SCAN_THREADS) priv[t] = 0;
+  __syncthreads();
+  for (uint64_t i = blockIdx.x * (uint64_t)SCAN_THREADS + threadIdx.x; i < n_seq; i += (uint64_t)gridDim.x * SCAN_THREADS) {
+    const uint32_t L = lens[i];
+    const uint64_t w0 = (uint64_t)offs[i] >> 5;
+    EnrichVisit<BOTH> v{erec, priv, scored, per, {}};
+    walk_sequence<BOTH>(words + w0, valid ? valid + w0 : nullptr, L, tab, mrec, nrec, v);
+  }
+  __syncthreads();
+  // private bin k of record k / per holds score top + k % per: bin top - thr + k % per of the motif (a bin above hi - thr
+  // is never added to and stays 0); then the scored sequences: one global atomic per motif and workgroup
+  for (int k = threadIdx.x; k < nrec * per; k += SCAN_THREADS) {
+    const uint32_t n = priv[k];
+    if (n) {
+      const int rr = k / per;
+      atomicAdd(&erec[rr].H[(int64_t)erec[rr].top - erec[rr].thr + (k - rr * per)], (unsigned long long)n);
+    }
+  }
+  for (int t = threadIdx.x; t < nrec; t += SCAN_THREADS)
+    if (scored[t]) atomicAdd(&scored_out[mrec[t].m], (unsigned long long)scored[t]);
+}
+
 // ---- first-order models (--dinuc) --------------------------------------------------------------------
 constexpr int PAIR_BINS = PENGK_MAX_MOTIF_LEN * 17;
 
@@ -1357,6 +1452,85 @@ double log10_binomial_sf(uint64_t n, uint64_t k, double p) {
   return ln / std::log(10.0);
 }
 
+// ---- the hypergeometric tail of --enrich (Loader 2000, "Fast and accurate computation of binomial probabilities") -----
+// stirlerr(n) = log(n!) - log(sqrt(2 pi n) (n / e)^n), n >= 1: the series in 1 / n above 15, lgamma below
+double stirlerr(double n) {
+  const double S0 = 1.0 / 12.0, S1 = 1.0 / 360.0, S2 = 1.0 / 1260.0, S3 = 1.0 / 1680.0, S4 = 1.0 / 1188.0;
+  const double HALF_LN_2PI = 0.918938533204672741780329736406;
+  if (n <= 15.0) return std::lgamma(n + 1.0) - (n + 0.5) * std::log(n) + n - HALF_LN_2PI;
+  const double nn = n * n;
+  if (n > 500.0) return (S0 - S1 / nn) / n;
+  if (n > 80.0) return (S0 - (S1 - S2 / nn) / nn) / n;
+  if (n > 35.0) return (S0 - (S1 - (S2 - S3 / nn) / nn) / nn) / n;
+  return (S0 - (S1 - (S2 - (S3 - S4 / nn) / nn) / nn) / nn) / n;
+}
+
+// bd0(x, np) = x log(x / np) + np - x, x > 0, np > 0: by its series in (x - np) / (x + np) where the direct form cancels
+double bd0(double x, double np) {
+  if (std::fabs(x - np) < 0.1 * (x + np)) {
+    double v = (x - np) / (x + np);
+    double s = (x - np) * v, ej = 2.0 * x * v;
+    v = v * v;
+    for (int j = 1; j < 1000; ++j) {
+      ej *= v;
+      const double s1 = s + ej / (double)(2 * j + 1);
+      if (s1 == s) return s1;
+      s = s1;
+    }
+    return s;
+  }
+  return x * std::log(x / np) + np - x;
+}
+
+// log of the Binomial(n, p) point mass at x (q = 1 - p, given apart so that neither is formed by a cancelling difference)
+double log_dbinom(double x, double n, double p, double q) {
+  if (p == 0.0) return x == 0.0 ? 0.0 : -INFINITY;
+  if (q == 0.0) return x == n ? 0.0 : -INFINITY;
+  if (x == 0.0) return n == 0.0 ? 0.0 : n * (p < 0.5 ? std::log1p(-p) : std::log(q));
+  if (x == n) return n * (q < 0.5 ? std::log1p(-q) : std::log(p));
+  const double lc = stirlerr(n) - stirlerr(x) - stirlerr(n - x) - bd0(x, n * p) - bd0(n - x, n * q);
+  const double lf = 1.837877066409345483560659472811 + std::log(x) + std::log1p(-x / n);  // log(2 pi x (n - x) / n)
+  return lc - 0.5 * lf;
+}
+
+// log P(X = x), X ~ Hypergeometric(N, K marked, n drawn), x inside the support: three binomial point masses at p = n / N
+double log_dhyper(uint64_t N, uint64_t K, uint64_t n, uint64_t x) {
+  const double p = (double)n / (double)N, q = (double)(N - n) / (double)N;
+  return log_dbinom((double)x, (double)K, p, q) + log_dbinom((double)(n - x), (double)(N - K), p, q) -
+         log_dbinom((double)n, (double)N, p, q);
+}
+
+// log10 P(X >= k) for the same X.  The point mass at the end of the shorter tail, then the ratio recurrence away from the
+// mode, its terms relative to that point mass (they fall from 1.0: nothing under- or overflows): upwards from k when the
+// terms fall from k on, else downwards from k - 1 and the complement.
+double log10_hypergeom_sf(uint64_t N, uint64_t K, uint64_t n, uint64_t k) {
+  const uint64_t lo = n + K > N ? n + K - N : 0, hi = std::min(K, n);
+  if (k <= lo) return 0.0;
+  if (k > hi) return -INFINITY;
+  const double dN = (double)N, dK = (double)K, dn = (double)n;
+  // P(x + 1) / P(x) = (K - x)(n - x) / ((x + 1)(N - K - n + x + 1))
+  auto up = [&](double x) { return (dK - x) * (dn - x) / ((x + 1.0) * (dN - dK - dn + x + 1.0)); };
+  const double LN10 = std::log(10.0);
+  if (up((double)k) <= 1.0) {
+    double term = 1.0, sum = 1.0;
+    for (uint64_t x = k; x < hi; ++x) {
+      term *= up((double)x);
+      sum += term;
+      if (term < sum * 1e-18) break;
+    }
+    return (log_dhyper(N, K, n, k) + std::log(sum)) / LN10;
+  }
+  // (k is at or below the mode: k - 1 >= lo is below it)
+  double term = 1.0, sum = 1.0;
+  for (uint64_t x = k - 1; x > lo; --x) {
+    term /= up((double)(x - 1));
+    sum += term;
+    if (term < sum * 1e-18) break;
+  }
+  const double lower = std::exp(log_dhyper(N, K, n, k - 1) + std::log(sum));
+  return lower < 1.0 ? std::log1p(-lower) / LN10 : -INFINITY;
+}
+
 }  // namespace
 }  // namespace pengk
 
@@ -1683,6 +1857,116 @@ int pengk_sites_histograms(pengk_ctx* ctx, const uint64_t* d_words, const uint32
     hipLaunchKernelGGL(motif_sites_hist_kernel<false>, grid, dim3(SCAN_THREADS), 0, ctx->stream, d_words, d_valid, d_offs, d_lens,
                        n_seq, st.tables, st.recs, st.groups, st.thr, d_hi, d_ho, h, t, c);
   PENGK_HIP(hipGetLastError());
+  return PENGK_OK;
+}
+
+int pengk_motif_enrich(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_valid, const int64_t* d_offs,
+                       const uint32_t* d_lens, uint64_t n_seq, int n_motifs, const int32_t* h_S, const int32_t* h_len,
+                       int both_strands, const int32_t* h_thr, const int32_t* h_hi, const uint64_t* h_hist_offs,
+                       uint64_t* d_hist, uint64_t* d_scored) {
+  if (!ctx || n_motifs < 0 || (n_motifs && (!h_S || !h_len || !h_thr || !h_hi || !h_hist_offs || !d_scored)) ||
+      (n_seq && n_motifs && (!d_words || !d_offs || !d_lens)))
+    return fail(PENGK_ERR_ARG, "pengk_motif_enrich: bad argument");
+  // (what keeps a 32-bit private bin from wrapping without a flush inside the loop: a sequence adds once per motif)
+  if (n_seq >= (1ull << 32)) return fail(PENGK_ERR_ARG, "pengk_motif_enrich: n_seq %llu (below 2^32)", (unsigned long long)n_seq);
+  int rc = check_motifs("pengk_motif_enrich", n_motifs, h_S, h_len);
+  if (rc) return rc;
+  // every score must have its bin: h_hi[m] at or above the sum of the column maxima, and bins to add to
+  for (int m = 0; m < n_motifs; ++m) {
+    int32_t mx = 0;
+    for (int j = 0; j < h_len[m]; ++j) {
+      const int32_t* c = h_S + ((size_t)m * PENGK_MAX_MOTIF_LEN + j) * 4;
+      mx += std::max(std::max(c[0], c[1]), std::max(c[2], c[3]));
+    }
+    if (h_hi[m] < mx) return fail(PENGK_ERR_ARG, "pengk_motif_enrich: motif %d: hi %d below its best score %d", m, h_hi[m], mx);
+    if (h_hi[m] >= h_thr[m] && !d_hist) return fail(PENGK_ERR_ARG, "pengk_motif_enrich: bad argument");
+  }
+  SCORE_ENTER(ctx);
+  if (n_seq == 0 || n_motifs == 0) return PENGK_OK;
+  const int strands = both_strands ? 2 : 1;
+  const int64_t per_launch = ctx->enrich_groups_per_launch;
+  unsigned long long* h = (unsigned long long*)d_hist;
+  unsigned long long* sc = (unsigned long long*)d_scored;
+  // batches of whole motif groups: the groups are stage_motifs' (greedy, in motif order), so a batch that starts where a
+  // group starts is cut into the groups the whole set would be cut into
+  for (int m0 = 0; m0 < n_motifs;) {
+    int m1 = m0, ints = 0;
+    int64_t n_groups = 1;
+    for (; m1 < n_motifs; ++m1) {
+      const int need = (h_len[m1] + 3) / 4 * strands * 256;
+      if (ints + need > SCAN_TABLES * 256) {
+        if (n_groups == per_launch) break;
+        ++n_groups;
+        ints = 0;
+      }
+      ints += need;
+    }
+    const int nb = m1 - m0;
+    const size_t hb = ((size_t)nb * sizeof(int32_t) + 7) & ~(size_t)7;
+    std::vector<char> staged(hb + (size_t)nb * sizeof(uint64_t));
+    memcpy(staged.data(), h_hi + m0, (size_t)nb * sizeof(int32_t));
+    memcpy(staged.data() + hb, h_hist_offs + m0, (size_t)nb * sizeof(uint64_t));
+    rc = ensure_scratch(ctx, &ctx->d_misc, &ctx->misc_bytes, staged.size());
+    if (rc) return rc;
+    StagedMotifs st;
+    rc = stage_motifs(ctx, nb, h_S + (size_t)m0 * PENGK_MAX_MOTIF_LEN * 4, h_len + m0, strands, h_thr + m0, &st);  // (synchronises)
+    if (rc) return rc;
+    if (st.n_groups != (int)n_groups) return fail(PENGK_ERR_RANGE, "pengk_motif_enrich: %d groups staged, %d planned", st.n_groups, (int)n_groups);
+    PENGK_HIP(hipMemcpy(ctx->d_misc, staged.data(), staged.size(), hipMemcpyHostToDevice));
+    const int32_t* d_hi = (const int32_t*)ctx->d_misc;
+    const uint64_t* d_ho = (const uint64_t*)((char*)ctx->d_misc + hb);
+    const dim3 grid(grid_for(ctx, n_seq, SCAN_THREADS, 8), (unsigned)st.n_groups);
+    // (the records carry motif indices within the batch: the scored counters are passed from the batch's first motif on;
+    // the histogram offsets are the caller's, from d_hist)
+    if (both_strands)
+      hipLaunchKernelGGL(motif_enrich_kernel<true>, grid, dim3(SCAN_THREADS), 0, ctx->stream, d_words, d_valid, d_offs, d_lens, n_seq,
+                         st.tables, st.recs, st.groups, st.thr, d_hi, d_ho, h, sc + m0);
+    else
+      hipLaunchKernelGGL(motif_enrich_kernel<false>, grid, dim3(SCAN_THREADS), 0, ctx->stream, d_words, d_valid, d_offs, d_lens, n_seq,
+                         st.tables, st.recs, st.groups, st.thr, d_hi, d_ho, h, sc + m0);
+    PENGK_HIP(hipGetLastError());
+    m0 = m1;
+  }
+  return PENGK_OK;
+}
+
+int pengk_hypergeom_log10_sf(uint64_t N, uint64_t K, uint64_t n, uint64_t k, double* out) {
+  if (!out || K > N || n > N) return fail(PENGK_ERR_ARG, "pengk_hypergeom_log10_sf: bad argument");
+  *out = log10_hypergeom_sf(N, K, n, k);
+  return PENGK_OK;
+}
+
+int pengk_enrich_summary(const uint64_t* h_pos, const uint64_t* h_neg, uint64_t nbins, int32_t thr, uint64_t n_pos,
+                         uint64_t n_neg, pengk_enrichment* out) {
+  if (!out || (nbins && (!h_pos || !h_neg)) || nbins > (1ull << 31) || (int64_t)thr + (int64_t)nbins > (int64_t)INT32_MAX ||
+      n_pos + n_neg < n_pos)
+    return fail(PENGK_ERR_ARG, "pengk_enrich_summary: bad argument");
+  uint64_t a = 0, b = 0;
+  for (uint64_t k = 0; k < nbins; ++k) {
+    if (h_pos[k] > n_pos - a || h_neg[k] > n_neg - b)
+      return fail(PENGK_ERR_ARG, "pengk_enrich_summary: more hits than scored sequences");
+    a += h_pos[k];
+    b += h_neg[k];
+  }
+  memset(out, 0, sizeof *out);
+  out->threshold = (int32_t)((int64_t)thr + (int64_t)nbins);
+  const uint64_t N = n_pos + n_neg;
+  a = b = 0;
+  for (uint64_t k = nbins; k-- > 0;) {
+    a += h_pos[k];
+    b += h_neg[k];
+    if (h_pos[k] + h_neg[k] == 0) continue;  // (the tail of the threshold above: not a test of its own)
+    const double lp = log10_hypergeom_sf(N, a + b, n_pos, a);
+    if (out->n_thresholds == 0 || lp < out->log10_pvalue) {  // (from the top down: the higher threshold wins a tie)
+      out->threshold = (int32_t)((int64_t)thr + (int64_t)k);
+      out->pos_hits = a;
+      out->neg_hits = b;
+      out->log10_pvalue = lp;
+    }
+    ++out->n_thresholds;
+  }
+  out->enrichment = (((double)out->pos_hits + 1.0) / ((double)n_pos + 1.0)) / (((double)out->neg_hits + 1.0) / ((double)n_neg + 1.0));
+  out->log10_adj_pvalue = out->n_thresholds ? std::min(0.0, out->log10_pvalue + std::log10((double)out->n_thresholds)) : 0.0;
   return PENGK_OK;
 }
 

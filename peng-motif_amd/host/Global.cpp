@@ -66,6 +66,11 @@ char* Global::compareDbFilename = nullptr;
 double Global::compareEvalue = 1.0;
 int Global::compareMinOverlap = 5;
 std::vector<MemeMotif> Global::compareDb;
+char* Global::enrichFilename = nullptr;
+char* Global::enrichDbFilename = nullptr;
+double Global::enrichPvalue = 1e-3;
+double Global::enrichEvalue = 10.0;
+std::vector<MemeMotif> Global::enrichDb;
 char* Global::spacingFilename = nullptr;
 double Global::spacingPvalue = 1e-4;
 int Global::spacingMaxGap = 150;
@@ -74,13 +79,14 @@ int Global::spacingMotifs = 16;
 void Global::init(int nargs, char* args[]) {
   readArguments(nargs, args);
   readCompareDb();  // (a database that cannot be used ends the run before the input is read)
+  readEnrichDb();
   Alphabet::init(alphabetType);
   pengk_host::start_context();  // the device runtime starts while the FASTA files are read
   pengk_host::start_sharded_ingest();  // multi-GPU run: every rank reads its own byte range of the files
-  // (the scoring, the sites, the centrality, the refinement, the spacing and the first-order models scan the input after
-  // the motifs are found)
+  // (the scoring, the sites, the centrality, the refinement, the spacing, the first-order models and the database
+  // enrichment scan the input after the motifs are found)
   pengk_host::keep_host_codes(scoreMotifs || sitesFilename || centralityFilename || refineFilename || spacingFilename ||
-                              dinucFilename);
+                              dinucFilename || enrichFilename);
   // both strands are handled inside the count; sequences are always read single stranded
   // ... and every chunk of the input set is packed and sent to the device while the rest is still being read
   pengk_host::begin_streaming_pack(patternLength);
@@ -133,6 +139,15 @@ void Global::readCompareDb() {
   std::string err;
   if (!read_meme_db(compareDbFilename, PENGK_MAX_MOTIF_LEN, &compareDb, &err)) {
     if (pengk_host::rank() == 0) log_line("ERROR", "--compare-db: " + err);
+    exit(4);
+  }
+}
+
+void Global::readEnrichDb() {
+  if (!enrichDbFilename) return;
+  std::string err;
+  if (!read_meme_db(enrichDbFilename, PENGK_MAX_MOTIF_LEN, &enrichDb, &err)) {
+    if (pengk_host::rank() == 0) log_line("ERROR", "--enrich-db: " + err);
     exit(4);
   }
 }
@@ -360,6 +375,28 @@ void Global::readArguments(int nargs, char* args[]) {
         exit(4);
       }
       compareMinOverlap = (int)n;
+    } else if (!strcmp(a, "--enrich")) {
+      enrichFilename = (char*)need(i, nargs, args, printHelp);
+    } else if (!strcmp(a, "--enrich-db")) {
+      enrichDbFilename = (char*)need(i, nargs, args, printHelp);
+    } else if (!strcmp(a, "--enrich-pvalue")) {
+      const char* v = need(i, nargs, args, printHelp);
+      char* end = nullptr;
+      enrichPvalue = std::strtod(v, &end);
+      if (end == v || *end || !(enrichPvalue > 0.0 && enrichPvalue <= 1.0)) {
+        printHelp();
+        log_line("ERROR", "--enrich-pvalue must be a number in (0, 1]");
+        exit(4);
+      }
+    } else if (!strcmp(a, "--enrich-evalue")) {
+      const char* v = need(i, nargs, args, printHelp);
+      char* end = nullptr;
+      enrichEvalue = std::strtod(v, &end);
+      if (end == v || *end || !(enrichEvalue > 0.0 && enrichEvalue <= 1e300)) {
+        printHelp();
+        log_line("ERROR", "--enrich-evalue must be a number above 0");
+        exit(4);
+      }
     } else if (!strcmp(a, "--spacing")) {
       spacingFilename = (char*)need(i, nargs, args, printHelp);
     } else if (!strcmp(a, "--spacing-pvalue")) {
@@ -400,6 +437,11 @@ void Global::readArguments(int nargs, char* args[]) {
   if (!compareFilename != !compareDbFilename) {
     printHelp();
     log_line("ERROR", compareFilename ? "--compare requires --compare-db" : "--compare-db requires --compare");
+    exit(4);
+  }
+  if (!enrichFilename != !enrichDbFilename) {
+    printHelp();
+    log_line("ERROR", enrichFilename ? "--enrich requires --enrich-db" : "--enrich-db requires --enrich");
     exit(4);
   }
 }
@@ -471,6 +513,12 @@ void Global::printHelp() {
   printf("  --compare-db FILE              the motif database, MEME format (requires --compare, and the reverse)\n");
   printf("  --compare-evalue FLOAT         only matches with an E-value at or below it are written (default 1)\n");
   printf("  --compare-min-overlap INT      columns an alignment must span, 1..64 (default 5)\n");
+  printf("  --enrich FILE                  test every motif of --enrich-db for enrichment in the input against its negatives\n");
+  printf("                                 (those of --score-motifs) and write the enriched ones (TSV: best-site threshold,\n");
+  printf("                                 hits, Fisher's exact test, adjusted p-, E- and q-value)\n");
+  printf("  --enrich-db FILE               the motif database, MEME format (requires --enrich, and the reverse)\n");
+  printf("  --enrich-pvalue FLOAT          p-value of the lowest site threshold tried, in (0, 1] (default 1e-3)\n");
+  printf("  --enrich-evalue FLOAT          only motifs with an E-value at or below it are written, above 0 (default 10)\n");
   printf("  --threads INT                  accepted for compatibility\n");
   printf("  --device INT                   HIP device index (default 0)\n");
   printf("  -v INT                         verbosity\n");

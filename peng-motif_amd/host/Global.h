@@ -82,6 +82,11 @@ class Global {
   static double compareEvalue;               // --compare-evalue
   static int compareMinOverlap;              // --compare-min-overlap
   static std::vector<MemeMotif> compareDb;   // ... the database, read before the sequences are
+  static char* enrichFilename;               // --enrich (new: the motifs of a MEME database tested for enrichment in the input)
+  static char* enrichDbFilename;             // --enrich-db
+  static double enrichPvalue;                // --enrich-pvalue
+  static double enrichEvalue;                // --enrich-evalue
+  static std::vector<MemeMotif> enrichDb;    // ... the database, read before the sequences are
   static char* spacingFilename;              // --spacing (new: co-occurrence and preferred gap of motif pairs)
   static double spacingPvalue;               // --spacing-pvalue
   static int spacingMaxGap;                  // --spacing-max-gap
@@ -93,6 +98,7 @@ class Global {
  private:
   static void readArguments(int nargs, char* args[]);
   static void readCompareDb();
+  static void readEnrichDb();
   static void printHelp();
 };
 

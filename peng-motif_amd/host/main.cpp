@@ -17,6 +17,7 @@
 #include "motif_centrality.h"
 #include "motif_compare.h"
 #include "motif_dinuc.h"
+#include "motif_enrich.h"
 #include "motif_refine.h"
 #include "motif_spacing.h"
 #include "motif_sites.h"
@@ -108,19 +109,27 @@ int main(int nargs, char** args) {
   clock.lap("process (count, sweep, hill-climb, PWMs, EM, merging)");
   peng.filter_redundancy(Global::mergeBitfactorThreshold, result);
   std::vector<MotifScore> scores;
-  // (the scoring, the sites, the centrality, the refinement, the spacing and the first-order models share one scan layout
-  // of the input)
+  // (the scoring, the sites, the centrality, the refinement, the spacing, the first-order models and the database
+  // enrichment share one scan layout of the input)
   std::unique_ptr<ScanInput> scan;
   if (Global::scoreMotifs || Global::sitesFilename || Global::centralityFilename || Global::refineFilename ||
-      Global::spacingFilename || Global::dinucFilename) {
+      Global::spacingFilename || Global::dinucFilename || Global::enrichFilename) {
     scan.reset(new ScanInput);
     build_scan_input(*Global::inputSequenceSet, scan.get());
+  }
+  // (--enrich scores against the negatives of --score-motifs and --dinuc: with it they are built once, for all three)
+  std::unique_ptr<Negatives> negatives;
+  if (Global::enrichFilename) {
+    negatives.reset(new Negatives);
+    build_negatives(*Global::inputSequenceSet, *scan, *bgModel, Global::bgModelOrder, Global::scoreSeed,
+                    Global::scoreNegativesShuffled, negatives.get());
   }
   if (Global::scoreMotifs) {
     // the writers' order first, then stable by zoops_score descending (scripts/shoot_peng.py re-ranks the motifs so)
     std::sort(result.begin(), result.end(), sort_IUPAC_patterns);
     scores = score_motifs(result, *Global::inputSequenceSet, *scan, *bgModel, Global::bgModelOrder,
-                          Global::strand == Strand::BOTH_STRANDS, Global::scoreSeed, Global::scoreNegativesShuffled);
+                          Global::strand == Strand::BOTH_STRANDS, Global::scoreSeed, Global::scoreNegativesShuffled,
+                          negatives.get());
     std::vector<size_t> order(result.size());
     for (size_t i = 0; i < order.size(); ++i) order[i] = i;
     std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return scores[a].zoops_score > scores[b].zoops_score; });
@@ -174,9 +183,18 @@ int main(int nargs, char** args) {
     ds.seed = Global::scoreSeed;
     ds.shuffled = Global::scoreNegativesShuffled;
     write_motif_dinuc(meme_order, *Global::inputSequenceSet, *scan, *bgModel, Global::strand == Strand::BOTH_STRANDS, ds,
-                      Global::dinucFilename, Global::dinucModelsFilename ? Global::dinucModelsFilename : "");
+                      Global::dinucFilename, Global::dinucModelsFilename ? Global::dinucModelsFilename : "", negatives.get());
     clock.lap("dinuc");
   }
+  if (Global::enrichFilename) {
+    EnrichSettings es;
+    es.pvalue = Global::enrichPvalue;
+    es.evalue = Global::enrichEvalue;
+    write_motif_enrich(Global::enrichDb, *scan, *negatives, *bgModel,
+                       Global::strand == Strand::BOTH_STRANDS, es, Global::enrichFilename);
+    clock.lap("enrich");
+  }
+  negatives.reset();
   scan.reset();
   // (the comparison reads neither the sequences nor their scan layout: rank 0 alone runs it)
   if (Global::compareFilename && pengk_host::rank() == 0) {

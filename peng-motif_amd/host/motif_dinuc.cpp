@@ -24,7 +24,7 @@ void write_file(const std::string& path, const std::string& o) {
 
 void write_motif_dinuc(const std::vector<IUPACPattern*>& pats, SequenceSet& set, const ScanInput& in, BackgroundModel& bg,
                        bool both_strands, const DinucSettings& ds, const std::string& report_path,
-                       const std::string& models_path) {
+                       const std::string& models_path, Negatives* shared) {
   using pengk_host::check;
   using pengk_host::DeviceBuffer;
   pengk_host::Lap lap("  dinuc: ");
@@ -98,8 +98,9 @@ void write_motif_dinuc(const std::vector<IUPACPattern*>& pats, SequenceSet& set,
   }
 
   // both models over the input and over the negatives of --score-motifs
-  Negatives neg;
-  build_negatives(set, in, bg, ds.bg_order, ds.seed, ds.shuffled, &neg);
+  Negatives own;
+  if (!shared) build_negatives(set, in, bg, ds.bg_order, ds.seed, ds.shuffled, &own);
+  Negatives& neg = shared ? *shared : own;
   std::vector<double> auc((size_t)2 * std::max(n_motifs, 1), 0.0);
   for (int k = 0; k < 2; ++k) {
     std::vector<int32_t> lo(std::max(n_motifs, 1), 0), hi(std::max(n_motifs, 1), 0);

@@ -26,9 +26,10 @@ struct DinucSettings {
 // summed over the ranks, rank 0 writes.  Per motif: the threshold at ds.pvalue of its found PWM's log-odds, the best site
 // per sequence (pengk_motif_best_sites), the single and pair profiles with ds.flank, pengk_dinuc_model; then two
 // pengk_motif_scan_dinuc passes (D0, D1) over the input and over the negatives of score_motifs (build_negatives), their
-// histograms and AUCs.  report_path: the TSV; models_path: the models file, or empty.  Collective in a multi-rank run.
+// histograms and AUCs.  report_path: the TSV; models_path: the models file, or empty.  shared: those negatives, already
+// built (see score_motifs), else NULL.  Collective in a multi-rank run.
 void write_motif_dinuc(const std::vector<IUPACPattern*>& pats, SequenceSet& set, const ScanInput& in, BackgroundModel& bg,
                        bool both_strands, const DinucSettings& ds, const std::string& report_path,
-                       const std::string& models_path);
+                       const std::string& models_path, Negatives* shared = nullptr);
 
 #endif

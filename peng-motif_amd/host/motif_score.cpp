@@ -116,7 +116,8 @@ void build_negatives(SequenceSet& set, const ScanInput& in, BackgroundModel& bg,
 }
 
 std::vector<MotifScore> score_motifs(const std::vector<IUPACPattern*>& pats, SequenceSet& set, const ScanInput& in,
-                                     BackgroundModel& bg, int K, bool both_strands, uint64_t seed, bool shuffled) {
+                                     BackgroundModel& bg, int K, bool both_strands, uint64_t seed, bool shuffled,
+                                     Negatives* shared) {
   using pengk_host::check;
   using pengk_host::DeviceBuffer;
   pengk_host::Lap lap("  score: ");
@@ -151,8 +152,9 @@ std::vector<MotifScore> score_motifs(const std::vector<IUPACPattern*>& pats, Seq
         "pengk_motif_scan");
   check(pengk_score_histograms(ctx, n_motifs, d_best.get(), n_local, lo.data(), hi.data(), hoffs.data(), d_hist.get()),
         "pengk_score_histograms");
-  Negatives neg;
-  build_negatives(set, in, bg, K, seed, shuffled, &neg);
+  Negatives own;
+  if (!shared) build_negatives(set, in, bg, K, seed, shuffled, &own);
+  Negatives& neg = shared ? *shared : own;
   check(pengk_motif_scan(ctx, neg.d_words.get(), neg.valid_or_null(), in.d_offs.get(), in.d_lens.get(), n_local, n_motifs,
                          S.data(), len.data(), both, d_best.get()),
         "pengk_motif_scan");

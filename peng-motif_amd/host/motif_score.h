@@ -55,8 +55,10 @@ struct MotifScore {
 // histograms are summed over the ranks, so every rank gets the scores of the whole input.  K: the order of the
 // sampling model (--bg-model-order), V from bg.  shuffled (--score-negatives shuffled): the negative of a sequence is
 // its own dinucleotide-preserving shuffle (pengk_shuffle_sequences: same seed, same global indices) with validity bits
-// of its own, not a sample of the model.  Collective in a multi-rank run.
+// of its own, not a sample of the model.  shared: negatives already built with these settings (--enrich builds them once
+// for every step that scores against them), else NULL: built here.  Collective in a multi-rank run.
 std::vector<MotifScore> score_motifs(const std::vector<IUPACPattern*>& pats, SequenceSet& set, const ScanInput& in,
-                                     BackgroundModel& bg, int K, bool both_strands, uint64_t seed, bool shuffled = false);
+                                     BackgroundModel& bg, int K, bool both_strands, uint64_t seed, bool shuffled = false,
+                                     Negatives* shared = nullptr);
 
 #endif
