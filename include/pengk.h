@@ -218,6 +218,21 @@ int pengk_pattern_stats(pengk_ctx* ctx, int W, int both_strands, int k, int max_
                         const uint64_t* d_ltot, const uint32_t* d_counts, float* d_bgprob, float* d_expected,
                         float* d_logp, float* d_z);
 
+/* The same sweep held to a SECOND null, a control set's own counts (this project's own; the reference has no such
+ * mode: INTEGRATION.md 7l).  d_ctrl_counts: uint32[4^W], the control's k-mer counts -- pengk_count under
+ * the same strand setting, mirrored as d_counts is (an un-mirrored table is legal: the value is defined per pattern,
+ * each twin gets its own); d_ctrl_ltot: the control's uint64 window total Lc; pseudocount a: finite, >= 0.
+ * With p_o[x] the value pengk_pattern_stats writes to bgprob[o][x], for every order o <= max_k
+ *     q_o[x] = (float) fmax( (double) p_o[x], ((double) c[x] + a) / (double) Lc )        (Lc == 0: q_o[x] = p_o[x])
+ * -- sum and quotient in fp64, one rounding to float32.  d_bgprob receives q_o; expected, log-p and z are made of
+ * q_k[x], the INPUT's ltot and the input's counts exactly as pengk_pattern_stats makes them of p_k[x]: the expected
+ * count is the larger of what the Markov model predicts and what the control shows.  One pass, every table written
+ * once; every even W from 2 to 14; option sweep_pairs as for pengk_pattern_stats. */
+int pengk_pattern_stats_control(pengk_ctx* ctx, int W, int both_strands, int k, int max_k, const float* d_V,
+                                const uint64_t* d_ltot, const uint32_t* d_counts, const uint32_t* d_ctrl_counts,
+                                const uint64_t* d_ctrl_ltot, double pseudocount, float* d_bgprob, float* d_expected,
+                                float* d_logp, float* d_z);
+
 /* ---- seed candidates (first half of BasePattern::select_base_patterns, src/base_pattern.cpp:443-515) ----------------
  * The reference std::sorts all 4^W ids by z-score and walks the ranking down to the threshold (:458-466); only ids with
  * z >= z_threshold and count >= count_threshold can become seeds.  This call compacts exactly those on the device

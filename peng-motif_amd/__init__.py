@@ -25,7 +25,7 @@ EXPORTS = [
     "pengk_stream", "pengk_set_stream", "pengk_set_option", "pengk_get_info", "pengk_malloc", "pengk_free", "pengk_memcpy_h2d", "pengk_memcpy_d2h",
     "pengk_memset", "pengk_warmup", "pengk_host_alloc", "pengk_host_free", "pengk_timer_create", "pengk_timer_record", "pengk_timer_elapsed_ms", "pengk_timer_destroy",
     "pengk_pack", "pengk_pack_threads", "pengk_pack_append", "pengk_packed_free", "pengk_set_sequences", "pengk_synth_sizes", "pengk_synth_sequences",
-    "pengk_count", "pengk_count_bg", "pengk_mirror_counts", "pengk_bg_count", "pengk_bg_model", "pengk_pattern_stats",
+    "pengk_count", "pengk_count_bg", "pengk_mirror_counts", "pengk_bg_count", "pengk_bg_model", "pengk_pattern_stats", "pengk_pattern_stats_control",
     "pengk_seed_candidates", "pengk_iupac_aggregate", "pengk_em", "pengk_em_device", "pengk_test_em_generation", "pengk_sequential_sum_f32", "pengk_motif_similarity", "pengk_selftest_division",
     "pengk_comm_unique_id", "pengk_comm_init", "pengk_comm_init_env", "pengk_comm_info", "pengk_comm_init_abandoned", "pengk_comm_rccl_version", "pengk_comm_destroy",
     "pengk_allreduce_tables", "pengk_comm_check_bin_bound", "pengk_allgather",
@@ -134,6 +134,7 @@ def lib():
         L.pengk_bg_count.argtypes = [vp, vp]
         L.pengk_bg_model.argtypes = [vp, vp, C.c_int, vp, vp]
         L.pengk_pattern_stats.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]
+        L.pengk_pattern_stats_control.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_double, vp, vp, vp, vp]
         L.pengk_seed_candidates.argtypes = [vp, C.c_int, vp, vp, f32, u64, vp, vp, i64, C.POINTER(i64)]
         L.pengk_iupac_aggregate.argtypes = [vp, C.c_int, C.c_int, vp, i64, vp, vp, vp, vp]
         L.pengk_em.argtypes = [vp, C.c_int, i64, vp, f32, f32, C.c_int, vp, vp, vp, vp]
@@ -604,6 +605,18 @@ class Context:
         z = z if z is not None else self.empty(n, np.float32)
         _check(lib().pengk_pattern_stats(self.h, W, int(both), k, max_k, _ptr(V), _ptr(ltot), _ptr(counts), _ptr(bgprob),
                                          _ptr(expected), _ptr(logp), _ptr(z)))
+        return bgprob, expected, logp, z
+
+    def pattern_stats_control(self, W, both, k, max_k, V, ltot, counts, ctrl_counts, ctrl_ltot, pseudocount=1.0, bgprob=None,
+                              expected=None, logp=None, z=None):
+        """the sweep held to a control set's counts as a second null (pengk_pattern_stats_control)"""
+        n = 4 ** W
+        bgprob = bgprob if bgprob is not None else self.empty((max_k + 1, n), np.float32)
+        expected = expected if expected is not None else self.empty(n, np.float32)
+        logp = logp if logp is not None else self.empty(n, np.float32)
+        z = z if z is not None else self.empty(n, np.float32)
+        _check(lib().pengk_pattern_stats_control(self.h, W, int(both), k, max_k, _ptr(V), _ptr(ltot), _ptr(counts), _ptr(ctrl_counts),
+                                                 _ptr(ctrl_ltot), float(pseudocount), _ptr(bgprob), _ptr(expected), _ptr(logp), _ptr(z)))
         return bgprob, expected, logp, z
 
     def iupac_aggregate(self, W, both, ids, counts, bgp, expected):

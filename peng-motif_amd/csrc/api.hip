@@ -556,6 +556,20 @@ int pengk_pattern_stats(pengk_ctx* ctx, int W, int both, int k, int max_k, const
   return launch_stats(ctx, W, both ? 1 : 0, k, max_k, d_V, d_ltot, d_counts, d_bgprob, d_expected, d_logp, d_z);
 }
 
+int pengk_pattern_stats_control(pengk_ctx* ctx, int W, int both, int k, int max_k, const float* d_V, const uint64_t* d_ltot,
+                                const uint32_t* d_counts, const uint32_t* d_ctrl_counts, const uint64_t* d_ctrl_ltot,
+                                double pseudocount, float* d_bgprob, float* d_expected, float* d_logp, float* d_z) {
+  if (!ctx || !d_V || !d_ltot || !d_counts || !d_ctrl_counts || !d_ctrl_ltot || !d_bgprob || !d_expected || !d_logp || !d_z)
+    return fail(PENGK_ERR_ARG, "pengk_pattern_stats_control: NULL argument");
+  PENGK_ENTER(ctx);
+  if (!valid_w(W)) return fail(PENGK_ERR_ARG, "pattern length %d unsupported", W);
+  if (k < 0 || max_k > 2 || k > max_k || max_k > W - 1) return fail(PENGK_ERR_ARG, "background orders k=%d max_k=%d unsupported", k, max_k);
+  if (!(pseudocount >= 0.0) || pseudocount > 1.7976931348623157e308)
+    return fail(PENGK_ERR_ARG, "pengk_pattern_stats_control: pseudocount %g is not a finite number >= 0", pseudocount);
+  return launch_stats_control(ctx, W, both ? 1 : 0, k, max_k, d_V, d_ltot, d_counts, d_ctrl_counts, d_ctrl_ltot, pseudocount, d_bgprob,
+                              d_expected, d_logp, d_z);
+}
+
 int pengk_seed_candidates(pengk_ctx* ctx, int W, const float* d_z, const uint32_t* d_counts, float z_threshold,
                           uint64_t count_threshold, uint32_t* h_ids, float* h_z, int64_t capacity, int64_t* n_out) {
   if (!ctx || !d_z || !d_counts || !n_out || (capacity && (!h_ids || !h_z))) return fail(PENGK_ERR_ARG, "pengk_seed_candidates: NULL argument");

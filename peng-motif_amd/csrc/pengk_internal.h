@@ -144,6 +144,9 @@ int launch_synth(pengk_ctx* ctx, uint64_t seed, uint64_t seq0, uint64_t n_seq, u
                  uint64_t* d_words, uint64_t* d_items);
 int launch_stats(pengk_ctx* ctx, int W, int both, int k, int max_k, const float* d_V, const uint64_t* d_ltot,
                  const uint32_t* d_counts, float* d_bgprob, float* d_expected, float* d_logp, float* d_z);
+int launch_stats_control(pengk_ctx* ctx, int W, int both, int k, int max_k, const float* d_V, const uint64_t* d_ltot,
+                         const uint32_t* d_counts, const uint32_t* d_ctrl_counts, const uint64_t* d_ctrl_ltot, double pseudocount,
+                         float* d_bgprob, float* d_expected, float* d_logp, float* d_z);
 int launch_seed_candidates(pengk_ctx* ctx, int W, const float* d_z, const uint32_t* d_counts, float z_threshold,
                            uint64_t count_threshold, uint32_t cap, uint32_t* d_n, uint32_t* d_ids, float* d_zs);
 int launch_sequential_sum(pengk_ctx* ctx, const float* d_terms, uint64_t n_chains, uint64_t chain_len, float* d_out);

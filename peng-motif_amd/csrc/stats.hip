@@ -65,17 +65,38 @@ __device__ __forceinline__ void pattern_statistics(float pk, float fl, uint32_t 
   zz = (float)((double)((float)n - mu) / sqrt((double)mu));
 }
 
-template <int W>
+// The second null (pengk_pattern_stats_control): a control set's own counts.  Every order's aggregated
+// probability p_o[x] is raised to the control's share of the pattern, q_o[x] = (float)fmax((double)p_o[x], (c[x] + a) / Lc)
+// -- sum and quotient in fp64, ONE rounding to float32 -- and everything downstream (bgprob, expected, log-p, z) is made
+// of q.  The quotient does not depend on the order: one fp64 division per pattern.  Lc == 0 (an empty control): q = p.
+// The kernels take the control as an OPTIONAL last argument (a parameter pack of none or one): without it they have the
+// signature and the code they had -- same instructions, same registers, same LDS.
+struct Control {
+  const uint32_t* __restrict__ counts;
+  const unsigned long long* __restrict__ ltot_p;
+  double a;
+};
+
+__device__ __forceinline__ double control_share(uint32_t c, double a, double lc) {
+  return lc == 0.0 ? -__builtin_inf() : ((double)c + a) / lc;
+}
+__device__ __forceinline__ float control_max(float p, double share) { return (float)fmax((double)p, share); }
+__device__ __forceinline__ const Control& the_control(const Control& c) { return c; }
+
+template <int W, class... Ctrl>
 __global__ __launch_bounds__(256) void stats_kernel(int both, int k, int max_k, const float* __restrict__ V,
                                                     const unsigned long long* __restrict__ ltot_p,
                                                     const uint32_t* __restrict__ counts, float* __restrict__ bgprob,
                                                     float* __restrict__ expected, float* __restrict__ logp,
-                                                    float* __restrict__ z) {
+                                                    float* __restrict__ z, const Ctrl... ctrl_arg) {
   __shared__ float sV[84];
   if (threadIdx.x < 84) sV[threadIdx.x] = V[threadIdx.x];
   __syncthreads();
   constexpr uint32_t NP = 1u << (2 * W);
   const float fl = (float)(*ltot_p);
+  constexpr bool CTRL = sizeof...(Ctrl) != 0;
+  [[maybe_unused]] double lc = 0.0;
+  if constexpr (CTRL) lc = (double)(*the_control(ctrl_arg...).ltot_p);
   for (uint32_t x = blockIdx.x * blockDim.x + threadIdx.x; x < NP; x += gridDim.x * blockDim.x) {
     float p[3];
     bg_products<W>(x, sV, p[0], p[1], p[2], max_k);
@@ -89,6 +110,13 @@ __global__ __launch_bounds__(256) void stats_kernel(int both, int k, int max_k, 
         p[1] += q[1];
         p[2] += q[2];
       }
+    }
+    if constexpr (CTRL) {
+      const Control& ctrl = the_control(ctrl_arg...);
+      const double share = control_share(ctrl.counts[x], ctrl.a, lc);
+      p[0] = control_max(p[0], share);
+      p[1] = control_max(p[1], share);
+      p[2] = control_max(p[2], share);
     }
     bgprob[x] = p[0];
     if (max_k >= 1) bgprob[(size_t)NP + x] = p[1];
@@ -114,22 +142,32 @@ __global__ __launch_bounds__(256) void stats_kernel(int both, int k, int max_k, 
 // are evaluated pattern by pattern as above.
 constexpr uint32_t PAIR_THREADS = 1024, PAIR_TILE = 4096, PAIR_ROW = 65;  // (rows of 64 padded: the twin's place is the transposed one)
 constexpr uint32_t PAIR_PER = PAIR_TILE / PAIR_THREADS;
+// (under the control policy the kernel is HELD to the 64 registers of two workgroups per CU: left alone the compiler takes
+// 74, one workgroup per CU, 0.224 ms at W = 12 against 0.203 with the 80 bytes of scratch this costs -- DESIGN.md 20.
+// Without a control the bounds are the ones the launch bounds imply, and the kernel is the one it was.)
+#ifndef PENGK_PAIR_WAVES
+#define PENGK_PAIR_WAVES __attribute__((amdgpu_waves_per_eu(sizeof...(Ctrl) ? 8 : 4, 8)))
+#endif
 // Two workgroups per CU (50 KB of LDS, 16 waves each), so that one's arithmetic runs beside the other's stores: a thread keeps
 // its four patterns' results in registers, the twins' counts and then the twins' values go through ONE three-array buffer in
 // two rounds (probabilities; expected / log-p / z).  (A first version staged all six arrays at once: 116 KB, one workgroup
 // per CU, compute and store phases one after the other -- 0.35 ms at W = 12 against the per-pattern kernel's 0.236.)
-template <int W>
-__global__ __launch_bounds__(PAIR_THREADS) void stats_pair_kernel(const uint32_t* __restrict__ mids, uint32_t n_pair, int k, int max_k, const float* __restrict__ V,
+// With a control the twin's control count travels beside its count, in the buffer's second array; the thread's
+// p0 / p1 / p2 then hold what the TWIN gets (its own values are stored at once), which differs from its own exactly where
+// the control counts of the two differ.
+template <int W, class... Ctrl>
+__global__ __launch_bounds__(PAIR_THREADS) PENGK_PAIR_WAVES void stats_pair_kernel(const uint32_t* __restrict__ mids, uint32_t n_pair, int k, int max_k, const float* __restrict__ V,
                                                                 const unsigned long long* __restrict__ ltot_p,
                                                                 const uint32_t* __restrict__ counts, float* __restrict__ bgprob,
                                                                 float* __restrict__ expected, float* __restrict__ logp,
-                                                                float* __restrict__ z) {
+                                                                float* __restrict__ z, const Ctrl... ctrl_arg) {
   static_assert(W >= 8, "three low, three high digits and a middle");
   constexpr uint32_t NP = 1u << (2 * W);
   constexpr int MID = W - 6, HSHIFT = 2 * W - 6;
   __shared__ float sV[84];
   __shared__ float s_buf[3][64 * PAIR_ROW];
   uint32_t* s_cnt = reinterpret_cast<uint32_t*>(&s_buf[0][0]);  // (the twins' counts: read before the first value is staged)
+  [[maybe_unused]] uint32_t* s_ctl = reinterpret_cast<uint32_t*>(&s_buf[1][0]);  // (and their control counts)
   // (one workgroup per middle m <= rc(m), from a list: with workgroup = middle, half of them had nothing to do -- and which
   // half follows the middle's lowest digit, i.e. the XCD a workgroup lands on: two XCDs did half of the work)
   // The list: the n_pair middles m < rc(m), then the 4^((W-6)/2) middles that are their own twins.  A tile of the latter
@@ -143,6 +181,9 @@ __global__ __launch_bounds__(PAIR_THREADS) void stats_pair_kernel(const uint32_t
   const uint32_t mid = mids[entry], mid_tw = revcomp32(mid, MID);
   if (t < 84) sV[t] = V[t];
   const float fl = (float)(*ltot_p);
+  constexpr bool CTRL = sizeof...(Ctrl) != 0;
+  [[maybe_unused]] double lc = 0.0;
+  if constexpr (CTRL) lc = (double)(*the_control(ctrl_arg...).ltot_p);
   auto id_of = [&](uint32_t m, uint32_t i) { return (i & 63u) | (m << 6) | ((i >> 6) << HSHIFT); };
   auto row_of = [](uint32_t i) { return (i & 63u) + PAIR_ROW * (i >> 6); };
   auto twin_at = [](uint32_t i) { return revcomp32(i >> 6, 3) + PAIR_ROW * revcomp32(i & 63u, 3); };  // (rc hi, rc lo) of the other tile
@@ -151,6 +192,7 @@ __global__ __launch_bounds__(PAIR_THREADS) void stats_pair_kernel(const uint32_t
     for (uint32_t j = 0; j < PAIR_PER; ++j) {
       const uint32_t i = j * PAIR_THREADS + t;
       s_cnt[row_of(i)] = counts[id_of(mid_tw, i)];
+      if constexpr (CTRL) s_ctl[row_of(i)] = the_control(ctrl_arg...).counts[id_of(mid_tw, i)];
     }
   }
   __syncthreads();
@@ -168,23 +210,57 @@ __global__ __launch_bounds__(PAIR_THREADS) void stats_pair_kernel(const uint32_t
       p1[j] += q[1];
       p2[j] += q[2];
     }
-    const float pk = k == 0 ? p0[j] : (k == 1 ? p1[j] : p2[j]);
-    const uint32_t n = counts[x];
-    float mu, lp, zz;
-    pattern_statistics(pk, fl, n, mu, lp, zz);
-    bgprob[x] = p0[j];
-    if (max_k >= 1) bgprob[(size_t)NP + x] = p1[j];
-    if (max_k >= 2) bgprob[2 * (size_t)NP + x] = p2[j];
-    expected[x] = mu;
-    logp[x] = lp;
-    z[x] = zz;
-    // the twin: same probabilities and expected count; log-p and z too when it has the same count
-    mu_tw[j] = mu;
-    lp_tw[j] = lp;
-    z_tw[j] = zz;
-    if (!own_twin) {
-      const uint32_t n_tw = s_cnt[twin_at(i)];
-      if (n_tw != n) pattern_statistics(pk, fl, n_tw, mu_tw[j], lp_tw[j], z_tw[j]);
+    if constexpr (CTRL) {
+      const Control& ctrl = the_control(ctrl_arg...);
+      // own values: stored at once; p0 / p1 / p2 keep the TWIN's, which differ where its control count does
+      const uint32_t c = ctrl.counts[x], c_tw = own_twin ? c : s_ctl[twin_at(i)];
+      const bool other = c_tw != c;
+      float pk;
+      {
+        const double share = control_share(c, ctrl.a, lc);
+        const float own0 = control_max(p0[j], share), own1 = control_max(p1[j], share), own2 = control_max(p2[j], share);
+        bgprob[x] = own0;
+        if (max_k >= 1) bgprob[(size_t)NP + x] = own1;
+        if (max_k >= 2) bgprob[2 * (size_t)NP + x] = own2;
+        pk = k == 0 ? own0 : (k == 1 ? own1 : own2);
+        const double share_tw = other ? control_share(c_tw, ctrl.a, lc) : share;
+        p0[j] = control_max(p0[j], share_tw);
+        p1[j] = control_max(p1[j], share_tw);
+        p2[j] = control_max(p2[j], share_tw);
+      }
+      const uint32_t n = counts[x];
+      float mu, lp, zz;
+      pattern_statistics(pk, fl, n, mu, lp, zz);
+      expected[x] = mu;
+      logp[x] = lp;
+      z[x] = zz;
+      mu_tw[j] = mu;
+      lp_tw[j] = lp;
+      z_tw[j] = zz;
+      if (!own_twin) {
+        const uint32_t n_tw = s_cnt[twin_at(i)];
+        if (n_tw != n || other)
+          pattern_statistics(k == 0 ? p0[j] : (k == 1 ? p1[j] : p2[j]), fl, n_tw, mu_tw[j], lp_tw[j], z_tw[j]);
+      }
+    } else {
+      const float pk = k == 0 ? p0[j] : (k == 1 ? p1[j] : p2[j]);
+      const uint32_t n = counts[x];
+      float mu, lp, zz;
+      pattern_statistics(pk, fl, n, mu, lp, zz);
+      bgprob[x] = p0[j];
+      if (max_k >= 1) bgprob[(size_t)NP + x] = p1[j];
+      if (max_k >= 2) bgprob[2 * (size_t)NP + x] = p2[j];
+      expected[x] = mu;
+      logp[x] = lp;
+      z[x] = zz;
+      // the twin: same probabilities and expected count; log-p and z too when it has the same count
+      mu_tw[j] = mu;
+      lp_tw[j] = lp;
+      z_tw[j] = zz;
+      if (!own_twin) {
+        const uint32_t n_tw = s_cnt[twin_at(i)];
+        if (n_tw != n) pattern_statistics(pk, fl, n_tw, mu_tw[j], lp_tw[j], z_tw[j]);
+      }
     }
   }
   if (own_twin) return;
@@ -222,9 +298,9 @@ __global__ __launch_bounds__(PAIR_THREADS) void stats_pair_kernel(const uint32_t
   }
 }
 
-template <int W>
+template <int W, class... Ctrl>
 int launch_w(pengk_ctx* ctx, int both, int k, int max_k, const float* d_V, const uint64_t* d_ltot, const uint32_t* d_counts,
-             float* d_bgprob, float* d_expected, float* d_logp, float* d_z) {
+             float* d_bgprob, float* d_expected, float* d_logp, float* d_z, const Ctrl... ctrl) {
   if constexpr (W >= 12) {
     if (both && ctx->sweep_pairs) {
       constexpr uint32_t n_mid = 1u << (2 * (W - 6)), n_pal = 1u << (W - 6), n_wg = (n_mid + n_pal) / 2u;  // (4^(m/2) middles are their own twins)
@@ -242,8 +318,8 @@ int launch_w(pengk_ctx* ctx, int both, int k, int max_k, const float* d_V, const
         PENGK_HIP(hipStreamSynchronize(ctx->stream));  // (the list leaves scope; once per context and pattern length)
         ctx->pair_mids_W = W;
       }
-      hipLaunchKernelGGL((stats_pair_kernel<W>), dim3(n_wg - n_pal + n_pal * PAIR_PER), dim3(PAIR_THREADS), 0, ctx->stream, (const uint32_t*)ctx->d_pair_mids, n_wg - n_pal, k, max_k, d_V,
-                         (const unsigned long long*)d_ltot, d_counts, d_bgprob, d_expected, d_logp, d_z);
+      hipLaunchKernelGGL((stats_pair_kernel<W, Ctrl...>), dim3(n_wg - n_pal + n_pal * PAIR_PER), dim3(PAIR_THREADS), 0, ctx->stream, (const uint32_t*)ctx->d_pair_mids, n_wg - n_pal, k, max_k, d_V,
+                         (const unsigned long long*)d_ltot, d_counts, d_bgprob, d_expected, d_logp, d_z, ctrl...);
       PENGK_HIP(hipGetLastError());
       return PENGK_OK;
     }
@@ -251,8 +327,8 @@ int launch_w(pengk_ctx* ctx, int both, int k, int max_k, const float* d_V, const
   const uint32_t np = 1u << (2 * W);
   const uint32_t need = (np + 255) / 256;
   const uint32_t cap = (uint32_t)ctx->num_cu * 16u;
-  hipLaunchKernelGGL((stats_kernel<W>), dim3(need < cap ? need : cap), dim3(256), 0, ctx->stream, both, k, max_k, d_V,
-                     (const unsigned long long*)d_ltot, d_counts, d_bgprob, d_expected, d_logp, d_z);
+  hipLaunchKernelGGL((stats_kernel<W, Ctrl...>), dim3(need < cap ? need : cap), dim3(256), 0, ctx->stream, both, k, max_k, d_V,
+                     (const unsigned long long*)d_ltot, d_counts, d_bgprob, d_expected, d_logp, d_z, ctrl...);
   PENGK_HIP(hipGetLastError());
   return PENGK_OK;
 }
@@ -287,6 +363,21 @@ __global__ __launch_bounds__(256) void seed_candidates_kernel(const float* __res
   }
 }
 
+template <class... Ctrl>
+int launch_stats_with(pengk_ctx* ctx, int W, int both, int k, int max_k, const float* d_V, const uint64_t* d_ltot,
+                      const uint32_t* d_counts, float* d_bgprob, float* d_expected, float* d_logp, float* d_z, const Ctrl... ctrl) {
+  switch (W) {
+    case 2: return launch_w<2>(ctx, both, k, max_k, d_V, d_ltot, d_counts, d_bgprob, d_expected, d_logp, d_z, ctrl...);
+    case 4: return launch_w<4>(ctx, both, k, max_k, d_V, d_ltot, d_counts, d_bgprob, d_expected, d_logp, d_z, ctrl...);
+    case 6: return launch_w<6>(ctx, both, k, max_k, d_V, d_ltot, d_counts, d_bgprob, d_expected, d_logp, d_z, ctrl...);
+    case 8: return launch_w<8>(ctx, both, k, max_k, d_V, d_ltot, d_counts, d_bgprob, d_expected, d_logp, d_z, ctrl...);
+    case 10: return launch_w<10>(ctx, both, k, max_k, d_V, d_ltot, d_counts, d_bgprob, d_expected, d_logp, d_z, ctrl...);
+    case 12: return launch_w<12>(ctx, both, k, max_k, d_V, d_ltot, d_counts, d_bgprob, d_expected, d_logp, d_z, ctrl...);
+    case 14: return launch_w<14>(ctx, both, k, max_k, d_V, d_ltot, d_counts, d_bgprob, d_expected, d_logp, d_z, ctrl...);
+    default: return fail(PENGK_ERR_ARG, "pattern length %d unsupported", W);
+  }
+}
+
 }  // namespace
 
 int launch_seed_candidates(pengk_ctx* ctx, int W, const float* d_z, const uint32_t* d_counts, float z_threshold,
@@ -302,16 +393,14 @@ int launch_seed_candidates(pengk_ctx* ctx, int W, const float* d_z, const uint32
 
 int launch_stats(pengk_ctx* ctx, int W, int both, int k, int max_k, const float* d_V, const uint64_t* d_ltot,
                  const uint32_t* d_counts, float* d_bgprob, float* d_expected, float* d_logp, float* d_z) {
-  switch (W) {
-    case 2: return launch_w<2>(ctx, both, k, max_k, d_V, d_ltot, d_counts, d_bgprob, d_expected, d_logp, d_z);
-    case 4: return launch_w<4>(ctx, both, k, max_k, d_V, d_ltot, d_counts, d_bgprob, d_expected, d_logp, d_z);
-    case 6: return launch_w<6>(ctx, both, k, max_k, d_V, d_ltot, d_counts, d_bgprob, d_expected, d_logp, d_z);
-    case 8: return launch_w<8>(ctx, both, k, max_k, d_V, d_ltot, d_counts, d_bgprob, d_expected, d_logp, d_z);
-    case 10: return launch_w<10>(ctx, both, k, max_k, d_V, d_ltot, d_counts, d_bgprob, d_expected, d_logp, d_z);
-    case 12: return launch_w<12>(ctx, both, k, max_k, d_V, d_ltot, d_counts, d_bgprob, d_expected, d_logp, d_z);
-    case 14: return launch_w<14>(ctx, both, k, max_k, d_V, d_ltot, d_counts, d_bgprob, d_expected, d_logp, d_z);
-    default: return fail(PENGK_ERR_ARG, "pattern length %d unsupported", W);
-  }
+  return launch_stats_with(ctx, W, both, k, max_k, d_V, d_ltot, d_counts, d_bgprob, d_expected, d_logp, d_z);
+}
+
+int launch_stats_control(pengk_ctx* ctx, int W, int both, int k, int max_k, const float* d_V, const uint64_t* d_ltot,
+                         const uint32_t* d_counts, const uint32_t* d_ctrl_counts, const uint64_t* d_ctrl_ltot, double pseudocount,
+                         float* d_bgprob, float* d_expected, float* d_logp, float* d_z) {
+  return launch_stats_with(ctx, W, both, k, max_k, d_V, d_ltot, d_counts, d_bgprob, d_expected, d_logp, d_z,
+                           Control{d_ctrl_counts, (const unsigned long long*)d_ctrl_ltot, pseudocount});
 }
 
 // (pengk_warmup: loads this translation unit's code object ahead of its first launch)

@@ -4,6 +4,7 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <cmath>
 #include <cstring>
 #include <ctime>
 #include <iostream>
@@ -75,6 +76,8 @@ char* Global::spacingFilename = nullptr;
 double Global::spacingPvalue = 1e-4;
 int Global::spacingMaxGap = 150;
 int Global::spacingMotifs = 16;
+bool Global::discriminative = false;
+double Global::discriminativePseudocount = 1.0;
 
 void Global::init(int nargs, char* args[]) {
   readArguments(nargs, args);
@@ -419,6 +422,17 @@ void Global::readArguments(int nargs, char* args[]) {
         exit(4);
       }
       (gap ? spacingMaxGap : spacingMotifs) = (int)n;
+    } else if (!strcmp(a, "--discriminative")) {
+      discriminative = true;
+    } else if (!strcmp(a, "--discriminative-pseudocount")) {
+      const char* v = need(i, nargs, args, printHelp);
+      char* end = nullptr;
+      discriminativePseudocount = std::strtod(v, &end);
+      if (end == v || *end || !std::isfinite(discriminativePseudocount) || discriminativePseudocount < 0.0) {
+        printHelp();
+        log_line("ERROR", "--discriminative-pseudocount must be a finite number, 0 or above");
+        exit(4);
+      }
     } else if (!strcmp(a, "--version")) {
       std::cout << "peng_motif " << VERSION_NUMBER << std::endl;  // (src/Global.cpp:299-301: without the word)
       exit(0);
@@ -428,6 +442,11 @@ void Global::readArguments(int nargs, char* args[]) {
     } else {
       if (pengk_host::rank() == 0) log_line("WARNING", std::string("Ignoring unknown option ") + a);
     }
+  }
+  if (discriminative && !backgroundSequenceFilename) {
+    printHelp();
+    log_line("ERROR", "--discriminative requires --background-sequences (the control set)");
+    exit(4);
   }
   if (dinucModelsFilename && !dinucFilename) {
     printHelp();
@@ -454,6 +473,10 @@ void Global::printHelp() {
   printf("  -o FILE                        write motifs in short MEME format\n");
   printf("  -j FILE                        write motifs as JSON\n");
   printf("  --background-sequences FILE    FASTA file for the background model (default: SEQFILE)\n");
+  printf("  --discriminative               hold the k-mer enrichment to the counts of the --background-sequences file as\n");
+  printf("                                 well: the expected count of a k-mer is the larger of what the background\n");
+  printf("                                 model predicts and what that control set shows (requires --background-sequences)\n");
+  printf("  --discriminative-pseudocount FLOAT   added to every control count, 0 or above (default 1)\n");
   printf("  -w INT                         pattern length, even, 4..14 (default 10)\n");
   printf("  -t FLOAT                       z-score threshold for seed k-mers (default 10)\n");
   printf("  --count-threshold INT          minimum count of a seed k-mer (default 3)\n");

@@ -92,6 +92,9 @@ class Global {
   static int spacingMaxGap;                  // --spacing-max-gap
   static int spacingMotifs;                  // --spacing-motifs
 
+  static bool discriminative;                // --discriminative (new: the k-mer sweep held to the control set's counts)
+  static double discriminativePseudocount;   // --discriminative-pseudocount
+
   static void init(int nargs, char* args[]);
   static void destruct();
 

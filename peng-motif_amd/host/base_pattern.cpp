@@ -14,6 +14,7 @@
 #include <iomanip>
 #include <iostream>
 
+#include "Global.h"
 #include "ranked_prefix.h"
 #include "utils.h"
 
@@ -34,8 +35,44 @@ BasePattern::BasePattern(const size_t pattern_length, Strand s, const int k, con
   const int both = strand == Strand::BOTH_STRANDS;
   const size_t NP = number_patterns;
 
-  // ---- sequences -> 2-bit stream + scan items (host packer resolves the N / skip scan rule) ----------
   pengk_host::Lap lap("    ");
+  // ---- --discriminative: the control set's own k-mer counts, the sweep's second null -------------
+  // The background set is packed, attached and counted like the input -- same strand setting, same non-overlap rule,
+  // shard tables summed, twins mirrored -- into a table of its own; then the input is attached and everything goes on
+  // as without the flag, except that the sweep is pengk_pattern_stats_control.
+  const bool discriminative = Global::discriminative;
+  pengk_host::DeviceBuffer<uint32_t> d_ctrl_counts;
+  pengk_host::DeviceBuffer<uint64_t> d_ctrl_ltot(1);
+  uint64_t ctrl_ltot = 0;
+  if (discriminative) {
+    SequenceSet* control = Global::backgroundSequenceSet;
+    pengk_host::DeviceBuffer<uint64_t> d_cwords, d_citems;
+    pengk_packed pk;
+    check(pengk_pack(control->codes(), control->offsets(), (int64_t)control->getLocalN(), W, 0, &pk), "pengk_pack");
+    d_cwords.resize(pk.n_words);
+    d_citems.resize(pk.n_items + 1);
+    d_cwords.upload(pk.words, pk.n_words);
+    if (pk.n_items) d_citems.upload(pk.items, pk.n_items);
+    check(pengk_set_sequences(context(), d_cwords.get(), pk.n_words, d_citems.get(), pk.n_items, W, pk.item_windows,
+                              pk.max_bin_bound, pk.all_whole),
+          "pengk_set_sequences");
+    check(pengk_set_option(context(), "n_windows_hint", (int64_t)pk.n_windows), "pengk_set_option");
+    pengk_packed_free(&pk);
+    d_ctrl_counts.resize(NP);
+    check(pengk_count(context(), both, d_ctrl_counts.get(), d_ctrl_ltot.get()), "pengk_count");
+    if (pengk_host::launched()) {
+      check(pengk_comm_check_bin_bound(context()), "pengk_comm_check_bin_bound");
+      check(pengk_allreduce_tables(context(), W, d_ctrl_counts.get(), d_ctrl_ltot.get(), nullptr), "pengk_allreduce_tables");
+    }
+    if (both) check(pengk_mirror_counts(context(), W, d_ctrl_counts.get()), "pengk_mirror_counts");
+    d_ctrl_ltot.download(&ctrl_ltot, 1);  // (waits for the count: the control's stream and items leave scope here)
+    check(pengk_synchronize(context()), "pengk_synchronize");
+    lap("control set: pack, upload, count");
+    std::cout << "discriminative mode: k-mer enrichment is held to the control set's counts (" << ctrl_ltot
+              << " control windows, pseudocount " << Global::discriminativePseudocount << ")" << std::endl;
+  }
+
+  // ---- sequences -> 2-bit stream + scan items (host packer resolves the N / skip scan rule) ----------
   // multi-GPU run: the sequence set of this rank holds its shard of whole records only (sharded ingest,
   // shared/SequenceSet.h); the tables are summed below
   pengk_host::DeviceBuffer<uint64_t> d_words, d_items, d_ltot(1);
@@ -83,9 +120,16 @@ BasePattern::BasePattern(const size_t pattern_length, Strand s, const int k, con
   d_V.upload(hV, 84);
   d_bgprob.resize((size_t)(this->max_k + 1) * NP);
   d_expected.resize(NP);
-  check(pengk_pattern_stats(context(), W, both, this->k, this->max_k, d_V.get(), d_ltot.get(), d_counts.get(), d_bgprob.get(),
-                            d_expected.get(), d_logp.get(), d_z.get()),
-        "pengk_pattern_stats");
+  if (discriminative)
+    check(pengk_pattern_stats_control(context(), W, both, this->k, this->max_k, d_V.get(), d_ltot.get(), d_counts.get(),
+                                      d_ctrl_counts.get(), d_ctrl_ltot.get(), Global::discriminativePseudocount, d_bgprob.get(),
+                                      d_expected.get(), d_logp.get(), d_z.get()),
+          "pengk_pattern_stats_control");
+  else
+    check(pengk_pattern_stats(context(), W, both, this->k, this->max_k, d_V.get(), d_ltot.get(), d_counts.get(), d_bgprob.get(),
+                              d_expected.get(), d_logp.get(), d_z.get()),
+          "pengk_pattern_stats");
+  if (discriminative) check(pengk_synchronize(context()), "pengk_synchronize");  // (the control's table leaves scope with the constructor)
 
   if (lap.on) check(pengk_synchronize(context()), "pengk_synchronize");
   lap("count + sweep");
@@ -111,7 +155,13 @@ BasePattern::BasePattern(const size_t pattern_length, Strand s, const int k, con
       dump("z.f32", host_zscore(), NP * sizeof(float));
       dump("expected.f32", host_expected(), NP * sizeof(float));
       dump("V.f32", hV, sizeof hV);
-      const std::string meta = "ltot " + std::to_string(ltot) + "\nN " + std::to_string(n_sequences) + "\n";
+      std::string meta = "ltot " + std::to_string(ltot) + "\nN " + std::to_string(n_sequences) + "\n";
+      if (discriminative) {
+        std::vector<uint32_t> c(NP);
+        d_ctrl_counts.download(c.data(), NP);
+        dump("ctrl_counts.u32", c.data(), NP * sizeof(uint32_t));
+        meta += "ctrl_ltot " + std::to_string(ctrl_ltot) + "\n";
+      }
       dump("meta.txt", meta.data(), meta.size());
     }
   }
