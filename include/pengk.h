@@ -527,6 +527,34 @@ int pengk_sites_emit(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_
                      int both_strands, const int32_t* h_thr, const uint64_t* d_counts, uint64_t i0, uint64_t i1,
                      pengk_site* d_sites, uint64_t cap);
 
+/* ---- erasing sites and packing on the device (--erase: mask the sites of the found motifs and search what is left;
+ *      this project's own) -----------------------------------------------------------------------------
+ * Integer throughout: a numpy restatement and any sharding give the same bits.
+ * A site is what pengk_sites_count counts (same arguments, d_valid = NULL: every base of a sequence valid).  cover = the
+ * bases that lie in [p, p + w_m) of some site of some motif; every motif is judged against the INPUT validity, so a site
+ * of one motif does not hide a site of another within one call.  d_out_valid (the layout of d_valid, must differ from
+ * it) receives d_valid & ~cover for every word of every sequence, the bits at and beyond a sequence's end cleared.
+ * d_sites[m] (n_motifs uint64) and d_erased[0] (uint64) are ADDED to (caller-zeroed): the site window strands of motif m
+ * -- the row sums of pengk_sites_count -- and the bits that went from 1 to 0, each counted once whatever number of
+ * motifs covers it.  n_seq = 0 does nothing; n_motifs = 0 writes d_out_valid (nothing covered) and nothing else. */
+int pengk_mask_sites(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_valid, const int64_t* d_offs,
+                     const uint32_t* d_lens, uint64_t n_seq, int n_motifs, const int32_t* h_S, const int32_t* h_len,
+                     int both_strands, const int32_t* h_thr, uint32_t* d_out_valid, uint64_t* d_sites, uint64_t* d_erased);
+/* The host packer on the device: from the scan layout to the count layout, bit for bit what pengk_pack writes for the
+ * same sequences given as byte codes (a cleared validity bit = code 0): words[0 .. n_words), items[0 .. n_items), n_bases,
+ * n_windows, max_bin_bound, n_sequences, max_len and all_whole.  bg_counts are not produced (zero).
+ * pengk_pack_scan_sizes measures: `out` receives the figures (out->words / out->items stay NULL: the buffers are the
+ * caller's), d_seq_base[i] / d_seq_item[i] (n_seq uint64 each, caller-owned) the stored bases / items in front of
+ * sequence i.  PENGK_ERR_RANGE where pengk_pack gives it.  Synchronises with the host.
+ * pengk_pack_scan writes: d_out_words (out->n_words uint64; zeroed here) and d_out_items (out->n_items uint64) from the
+ * same input, W, item_windows and the two offset arrays; nothing at or beyond n_words / n_items is written.  Asynchronous
+ * on the context's stream.  Attach the result with pengk_set_sequences. */
+int pengk_pack_scan_sizes(pengk_ctx* ctx, const uint32_t* d_valid, const int64_t* d_offs, const uint32_t* d_lens, uint64_t n_seq,
+                          int W, int item_windows, uint64_t* d_seq_base, uint64_t* d_seq_item, pengk_packed* out);
+int pengk_pack_scan(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_valid, const int64_t* d_offs,
+                    const uint32_t* d_lens, uint64_t n_seq, int W, int item_windows, const uint64_t* d_seq_base,
+                    const uint64_t* d_seq_item, uint64_t* d_out_words, uint64_t n_words, uint64_t* d_out_items, uint64_t n_items);
+
 /* ---- central enrichment (--centrality: which found motifs sit at the centres of the input sequences; CentriMo's
  *      site distribution and binomial test) ------------------------------------------------------------
  * Over the scan layout and the integer log-odds of pengk_motif_scan.  One best window strand per (motif, sequence); the

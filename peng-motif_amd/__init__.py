@@ -36,6 +36,7 @@ EXPORTS = [
     "pengk_motif_scan", "pengk_score_histograms", "pengk_score_summary",
     "pengk_score_tail_pvalues", "pengk_score_threshold", "pengk_sites_count", "pengk_sites_slices", "pengk_sites_emit",
     "pengk_sites_histograms", "pengk_sites_qvalues", "pengk_qvalue_threshold",
+    "pengk_mask_sites", "pengk_pack_scan_sizes", "pengk_pack_scan",
     "pengk_motif_enrich", "pengk_hypergeom_log10_sf", "pengk_enrich_summary",
     "pengk_motif_best_sites", "pengk_centrality_histograms", "pengk_centrality_summary", "pengk_binomial_log10_sf",
     "pengk_site_profiles", "pengk_profile_refine",
@@ -169,6 +170,9 @@ def lib():
         L.pengk_sites_count.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, vp, vp, C.c_int, vp, vp]
         L.pengk_sites_histograms.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
         L.pengk_sites_qvalues.argtypes = [vp, u64, u64, vp, vp]
+        L.pengk_mask_sites.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]
+        L.pengk_pack_scan_sizes.argtypes = [vp, vp, vp, vp, u64, C.c_int, C.c_int, vp, vp, C.POINTER(PackedStruct)]
+        L.pengk_pack_scan.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, C.c_int, vp, vp, vp, u64, vp, u64]
         L.pengk_motif_enrich.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp]
         L.pengk_hypergeom_log10_sf.argtypes = [u64, u64, u64, u64, C.POINTER(C.c_double)]
         L.pengk_enrich_summary.argtypes = [vp, vp, u64, C.c_int32, u64, u64, C.POINTER(EnrichmentStruct)]
@@ -719,6 +723,44 @@ class Context:
         _check(lib().pengk_sites_count(self.h, _ptr(scan[0]), _ptr(scan[1]), _ptr(scan[2]), _ptr(scan[3]), scan[4], n,
                                        Sp.ctypes.data, ln.ctypes.data, int(both), th.ctypes.data, _ptr(counts)))
         return counts
+
+    # ---- erasing sites and packing on the device (--erase) --------------------------------------------------
+    def mask_sites(self, scan, S, lens, both, thr, all_valid=False, out_valid=None, sites=None, erased=None):
+        """(out_valid, sites, erased), all on the device: the validity words of `scan` with the sites of the motifs at
+        thresholds thr cleared (pengk_mask_sites), the site window strands per motif and the bits cleared.  all_valid:
+        d_valid = NULL.  sites / erased: device uint64 arrays to ADD to instead of fresh zeroed ones."""
+        n = len(lens)
+        Sp, ln = _pad_motifs(S, lens)
+        th = np.ascontiguousarray(thr, np.int32)
+        if out_valid is None:
+            out_valid = self.empty(scan[0].shape, np.uint32)
+        if sites is None:
+            sites = self.to_device(np.zeros(max(n, 1), np.uint64))
+        if erased is None:
+            erased = self.to_device(np.zeros(1, np.uint64))
+        _check(lib().pengk_mask_sites(self.h, _ptr(scan[0]), None if all_valid else _ptr(scan[1]), _ptr(scan[2]), _ptr(scan[3]),
+                                      scan[4], n, Sp.ctypes.data, ln.ctypes.data, int(both), th.ctypes.data, _ptr(out_valid),
+                                      _ptr(sites), _ptr(erased)))
+        return out_valid, sites, erased
+
+    def pack_scan(self, scan, W, item_windows=0, valid=None, all_valid=False, attach=False):
+        """the sequences of `scan` (under the validity words `valid` instead of its own, when given) in the count layout,
+        packed on the device: (words, items, figures) -- two device uint64 arrays and the PackedStruct of
+        pengk_pack_scan_sizes.  attach: pengk_set_sequences on the result, as Context.upload does for a host pack."""
+        v = None if all_valid else _ptr(valid if valid is not None else scan[1])
+        n = scan[4]
+        base, item = self.empty(max(n, 1), np.uint64), self.empty(max(n, 1), np.uint64)
+        st = PackedStruct()
+        _check(lib().pengk_pack_scan_sizes(self.h, v, _ptr(scan[2]), _ptr(scan[3]), n, W, item_windows, _ptr(base), _ptr(item),
+                                           C.byref(st)))
+        words, items = self.empty(st.n_words, np.uint64), self.empty(max(st.n_items, 1), np.uint64)
+        _check(lib().pengk_pack_scan(self.h, _ptr(scan[0]), v, _ptr(scan[2]), _ptr(scan[3]), n, W, item_windows, _ptr(base),
+                                     _ptr(item), _ptr(words), st.n_words, _ptr(items), st.n_items))
+        self.synchronize()  # (the offset arrays die with this call)
+        if attach:
+            self.set_sequences(words, items, st.n_words, st.n_items, st.W, st.item_windows, st.max_bin_bound, st.all_whole)
+            self.set_option("n_windows_hint", st.n_windows)
+        return words, items, st
 
     def sites_histograms(self, scan, S, lens, both, thr, hi, counts=None, hist=None, tests=None, offs=None):
         """(hists, tests): hists[m] (uint64, max(0, hi[m] - thr[m] + 1) bins) the sites of motif m by score - thr[m], tests[m]

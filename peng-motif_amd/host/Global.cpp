@@ -76,6 +76,9 @@ char* Global::spacingFilename = nullptr;
 double Global::spacingPvalue = 1e-4;
 int Global::spacingMaxGap = 150;
 int Global::spacingMotifs = 16;
+char* Global::eraseFilename = nullptr;
+int Global::eraseRounds = 1;
+double Global::erasePvalue = 1e-4;
 bool Global::discriminative = false;
 double Global::discriminativePseudocount = 1.0;
 
@@ -89,7 +92,7 @@ void Global::init(int nargs, char* args[]) {
   // (the scoring, the sites, the centrality, the refinement, the spacing, the first-order models and the database
   // enrichment scan the input after the motifs are found)
   pengk_host::keep_host_codes(scoreMotifs || sitesFilename || centralityFilename || refineFilename || spacingFilename ||
-                              dinucFilename || enrichFilename);
+                              dinucFilename || enrichFilename || eraseFilename);
   // both strands are handled inside the count; sequences are always read single stranded
   // ... and every chunk of the input set is packed and sent to the device while the rest is still being read
   pengk_host::begin_streaming_pack(patternLength);
@@ -422,6 +425,27 @@ void Global::readArguments(int nargs, char* args[]) {
         exit(4);
       }
       (gap ? spacingMaxGap : spacingMotifs) = (int)n;
+    } else if (!strcmp(a, "--erase")) {
+      eraseFilename = (char*)need(i, nargs, args, printHelp);
+    } else if (!strcmp(a, "--erase-rounds")) {
+      const char* v = need(i, nargs, args, printHelp);
+      char* end = nullptr;
+      const long n = std::strtol(v, &end, 10);
+      if (end == v || *end || n < 1 || n > 8) {
+        printHelp();
+        log_line("ERROR", "--erase-rounds must be an integer in [1, 8]");
+        exit(4);
+      }
+      eraseRounds = (int)n;
+    } else if (!strcmp(a, "--erase-pvalue")) {
+      const char* v = need(i, nargs, args, printHelp);
+      char* end = nullptr;
+      erasePvalue = std::strtod(v, &end);
+      if (end == v || *end || !(erasePvalue > 0.0 && erasePvalue <= 1.0)) {
+        printHelp();
+        log_line("ERROR", "--erase-pvalue must be a number in (0, 1]");
+        exit(4);
+      }
     } else if (!strcmp(a, "--discriminative")) {
       discriminative = true;
     } else if (!strcmp(a, "--discriminative-pseudocount")) {
@@ -477,6 +501,11 @@ void Global::printHelp() {
   printf("                                 well: the expected count of a k-mer is the larger of what the background\n");
   printf("                                 model predicts and what that control set shows (requires --background-sequences)\n");
   printf("  --discriminative-pseudocount FLOAT   added to every control count, 0 or above (default 1)\n");
+  printf("  --erase FILE                   after the search, mask the sites of the motifs found and search what is left\n");
+  printf("                                 again; the later rounds' motifs are appended.  FILE: one line per round and motif\n");
+  printf("  --erase-rounds INT             further rounds of --erase, 1..8 (default 1); a round that finds or erases\n");
+  printf("                                 nothing is the last\n");
+  printf("  --erase-pvalue FLOAT           p-value threshold of the sites that --erase masks, in (0, 1] (default 1e-4)\n");
   printf("  -w INT                         pattern length, even, 4..14 (default 10)\n");
   printf("  -t FLOAT                       z-score threshold for seed k-mers (default 10)\n");
   printf("  --count-threshold INT          minimum count of a seed k-mer (default 3)\n");

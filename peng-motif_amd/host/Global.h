@@ -92,6 +92,9 @@ class Global {
   static int spacingMaxGap;                  // --spacing-max-gap
   static int spacingMotifs;                  // --spacing-motifs
 
+  static char* eraseFilename;                // --erase (new: mask the found motifs' sites and search again)
+  static int eraseRounds;                    // --erase-rounds: further rounds, 1..8
+  static double erasePvalue;                 // --erase-pvalue
   static bool discriminative;                // --discriminative (new: the k-mer sweep held to the control set's counts)
   static double discriminativePseudocount;   // --discriminative-pseudocount
 

@@ -143,7 +143,7 @@ BasePattern::BasePattern(const size_t pattern_length, Strand s, const int k, con
   if (const char* dir = std::getenv("PENGK_DUMP_TABLES")) {
     if (pengk_host::rank() == 0) {
       auto dump = [&](const char* name, const void* p, size_t bytes) {
-        const std::string path = std::string(dir) + "/" + name;
+        const std::string path = std::string(dir) + "/" + pengk_host::dump_subdir() + name;  // (--erase: round<r>/)
         FILE* f = fopen(path.c_str(), "wb");
         if (!f || fwrite(p, 1, bytes, f) != bytes) {
           std::cerr << "Error: PENGK_DUMP_TABLES: cannot write " << path << std::endl;

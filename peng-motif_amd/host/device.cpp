@@ -357,7 +357,19 @@ const PackedInput* finish_streaming_pack(SequenceSet* set) {
   return &st->in;
 }
 
+static SequenceSet* g_override_set = nullptr;
+static const PackedInput* g_override = nullptr;
+static std::string g_dump_subdir;
+
+void override_packed_input(SequenceSet* set, const PackedInput* in) {
+  g_override_set = in ? set : nullptr;
+  g_override = in;
+}
+void set_dump_subdir(const std::string& sub) { g_dump_subdir = sub; }
+const std::string& dump_subdir() { return g_dump_subdir; }
+
 const PackedInput* packed_input(SequenceSet* set, int W) {
+  if (g_override && g_override_set == set && g_override->W == W) return g_override;
   Stream* st = g_stream;
   return st && st->set == set && st->in.W == W && st->in.d_words ? &st->in : nullptr;
 }

@@ -9,6 +9,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <iostream>
+#include <string>
 
 #include "pengk.h"
 
@@ -51,6 +52,12 @@ struct PackedInput {
 void begin_streaming_pack(int W);                              // the NEXT SequenceSet constructed is packed as it is read
 const PackedInput* finish_streaming_pack(::SequenceSet* set);    // waits for the last upload; nullptr if nothing was packed
 const PackedInput* packed_input(::SequenceSet* set, int W);      // of a set that went through the two calls above, else nullptr
+// --erase: from now on packed_input(set, W) hands out `in` (a masked copy of the set, packed on the device; the caller
+// owns it and its buffers) instead of what was packed during the read; nullptr ends that
+void override_packed_input(::SequenceSet* set, const PackedInput* in);
+// PENGK_DUMP_TABLES: the folder below the one it names that BasePattern writes into ("" = that folder itself)
+void set_dump_subdir(const std::string& sub);
+const std::string& dump_subdir();
 // the packed chunks keep their byte codes on the host (the motif scoring builds its own layout from them afterwards);
 // call before begin_streaming_pack
 void keep_host_codes(bool keep);

@@ -18,6 +18,7 @@
 #include "motif_compare.h"
 #include "motif_dinuc.h"
 #include "motif_enrich.h"
+#include "motif_erase.h"
 #include "motif_refine.h"
 #include "motif_spacing.h"
 #include "motif_sites.h"
@@ -105,17 +106,28 @@ int main(int nargs, char** args) {
   params.max_optimized_patterns = Global::maximum_optimized_patterns;
 
   std::vector<IUPACPattern*> result;
+  if (Global::eraseFilename)
+    std::cout << "erase mode: up to " << Global::eraseRounds << " further round" << (Global::eraseRounds == 1 ? "" : "s")
+              << " on the input with the found motifs' sites (p-value <= " << Global::erasePvalue << ") masked" << std::endl
+              << "erase round 1: the input as it is" << std::endl;
   peng.process(params, result);
   clock.lap("process (count, sweep, hill-climb, PWMs, EM, merging)");
   peng.filter_redundancy(Global::mergeBitfactorThreshold, result);
   std::vector<MotifScore> scores;
-  // (the scoring, the sites, the centrality, the refinement, the spacing, the first-order models and the database
-  // enrichment share one scan layout of the input)
+  // (the erasing, the scoring, the sites, the centrality, the refinement, the spacing, the first-order models and the
+  // database enrichment share one scan layout of the input)
   std::unique_ptr<ScanInput> scan;
   if (Global::scoreMotifs || Global::sitesFilename || Global::centralityFilename || Global::refineFilename ||
-      Global::spacingFilename || Global::dinucFilename || Global::enrichFilename) {
+      Global::spacingFilename || Global::dinucFilename || Global::enrichFilename || Global::eraseFilename) {
     scan.reset(new ScanInput);
     build_scan_input(*Global::inputSequenceSet, scan.get());
+  }
+  // --erase: further rounds on the masked input; their motifs join the list, and every report below sees the union over
+  // the unmasked scan input
+  if (Global::eraseFilename) {
+    run_erase_rounds(peng, params, result, *Global::inputSequenceSet, *scan, *bgModel, Global::strand == Strand::BOTH_STRANDS,
+                     Global::erasePvalue, Global::eraseRounds, Global::mergeBitfactorThreshold, Global::eraseFilename);
+    clock.lap("erase rounds");
   }
   // (--enrich scores against the negatives of --score-motifs and --dinuc: with it they are built once, for all three)
   std::unique_ptr<Negatives> negatives;

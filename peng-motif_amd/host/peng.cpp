@@ -318,6 +318,8 @@ void Peng::process(PengParameters& params, std::vector<IUPACPattern*>& best_iupa
   auto seeds = base->select_base_patterns(params.zscore_threshold, params.count_threshold, strand == Strand::PLUS_STRAND,
                                           params.filter_neighbors);
   if (seeds.empty()) std::cout << "No overrepresented seed patterns found. Stopping." << std::endl;
+  last_seeds = seeds.size();
+  last_windows = base->getLtot();
   lap("seed selection");
   base->print_patterns(seeds);
 

@@ -45,6 +45,8 @@ class Peng {
   ~Peng();
 
   void process(PengParameters& params, std::vector<IUPACPattern*>& best_iupac_patterns);
+  // of the last process(): the seeds past the thresholds (before --max-optimized-patterns cuts them) and the windows counted
+  size_t last_seeds = 0, last_windows = 0;
   void filter_redundancy(const float merge_bit_factor_threshold, std::vector<IUPACPattern*>& iupac_patterns);
   // scores (--score-motifs): one per pattern, in the order given, which the writers then keep
   void printShortMeme(std::vector<IUPACPattern*>& best_iupac_patterns, const std::string output_filename,
