@@ -555,6 +555,40 @@ int pengk_pack_scan(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_v
                     const uint32_t* d_lens, uint64_t n_seq, int W, int item_windows, const uint64_t* d_seq_base,
                     const uint64_t* d_seq_item, uint64_t* d_out_words, uint64_t n_words, uint64_t* d_out_items, uint64_t n_items);
 
+/* ---- a control set matched to the input (--score-negatives control: the negatives of the scoring steps are real
+ *      sequences, drawn from the control in proportion to the input's GC content and length, as HOMER and BiasAway
+ *      match theirs; this project's own definitions) -------------------------------------------------
+ * Integer throughout: a numpy restatement and any sharding give the same bits.  A subset of a scan layout is a shorter
+ * pair of offs / lens arrays into the same words, which every scan entry above accepts as it stands.
+ *
+ * The stratum of every sequence of a scan layout: d_stratum[i] (n_seq uint16) and its count, d_hist[stratum] (256
+ * uint64, ADDED to: caller-zeroed, shards and several calls sum exactly).  n = the valid bases of the sequence (d_valid =
+ * NULL: its length), gc = the C or G among them -- every other letter is stored as A and the words are zero beyond the
+ * end, so no validity word is read for it.  n = 0: stratum 0xFFFF, counted nowhere.  Else g = min(G - 1, (gc * G) / n),
+ * G = gc_bins in 1 .. 16; with L the length, l = floor(log2 L) and sub = the bit of L below its top bit (0 for L = 1),
+ * lb = clamp(2 l + sub - 10, 0, 15) -- half-octave length bins, everything below 48 bases in bin 0, everything from 6144
+ * on in bin 15 --, lb = 0 when use_length is 0; stratum = lb * G + g.  n_seq = 0 does nothing; n_seq >= 2^32, gc_bins
+ * outside 1 .. 16 and use_length other than 0 / 1 are PENGK_ERR_ARG.  Asynchronous on the context's stream. */
+int pengk_seq_strata(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_valid, const int64_t* d_offs,
+                     const uint32_t* d_lens, uint64_t n_seq, int gc_bins, int use_length, uint16_t* d_stratum, uint64_t* d_hist);
+/* Pure CPU.  From the input's and the control's stratum counts (256 uint64 each, summed over all ranks) and ratio R >= 1:
+ * h_quota[s] = min(h_ctrl[s], R * h_in[s]), the control sequences of stratum s to keep, and *shortfall_out = sum over s
+ * of R * h_in[s] - h_quota[s], what the control could not supply.  A product or a sum beyond 2^63 is PENGK_ERR_RANGE,
+ * R = 0 PENGK_ERR_ARG. */
+int pengk_match_quotas(const uint64_t* h_in, const uint64_t* h_ctrl, uint64_t ratio, uint64_t* h_quota, uint64_t* shortfall_out);
+/* The selection.  d_stratum: the strata of this call's n_seq sequences (pengk_seq_strata; an entry of 256 or above is never
+ * kept); h_count[s] the sequences of stratum s over ALL ranks, h_quota[s] <= h_count[s] how many of them to keep, h_rank0[s]
+ * how many of them the earlier ranks hold (256 uint64 each).  Sequence i of stratum s has the rank r = h_rank0[s] + the
+ * sequences j < i of this call with the same stratum -- a stable rank in file order -- and is kept iff
+ * ((r + 1) q) / c > (r q) / c in uint64 (q = h_quota[s], c = h_count[s]): even spacing through the file, exactly q kept
+ * over all shards, q = c keeps all, q = 0 none.  The kept sequences' d_offs[i] / d_lens[i] / i are written compacted, in
+ * file order, to d_sel_offs / d_sel_lens / d_sel_index (room for n_seq entries each); *n_sel_out = this call's count.
+ * n_seq = 0 does nothing.  PENGK_ERR_ARG: n_seq >= 2^32, an h_quota[s] > h_count[s], an h_count[s] >= 2^32, an
+ * h_rank0[s] > h_count[s].  Synchronises with the host. */
+int pengk_select_strata(pengk_ctx* ctx, const uint16_t* d_stratum, uint64_t n_seq, const uint64_t* h_count, const uint64_t* h_quota,
+                        const uint64_t* h_rank0, const int64_t* d_offs, const uint32_t* d_lens, int64_t* d_sel_offs,
+                        uint32_t* d_sel_lens, uint32_t* d_sel_index, uint64_t* n_sel_out);
+
 /* ---- central enrichment (--centrality: which found motifs sit at the centres of the input sequences; CentriMo's
  *      site distribution and binomial test) ------------------------------------------------------------
  * Over the scan layout and the integer log-odds of pengk_motif_scan.  One best window strand per (motif, sequence); the

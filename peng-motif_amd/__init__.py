@@ -37,6 +37,7 @@ EXPORTS = [
     "pengk_score_tail_pvalues", "pengk_score_threshold", "pengk_sites_count", "pengk_sites_slices", "pengk_sites_emit",
     "pengk_sites_histograms", "pengk_sites_qvalues", "pengk_qvalue_threshold",
     "pengk_mask_sites", "pengk_pack_scan_sizes", "pengk_pack_scan",
+    "pengk_seq_strata", "pengk_match_quotas", "pengk_select_strata",
     "pengk_motif_enrich", "pengk_hypergeom_log10_sf", "pengk_enrich_summary",
     "pengk_motif_best_sites", "pengk_centrality_histograms", "pengk_centrality_summary", "pengk_binomial_log10_sf",
     "pengk_site_profiles", "pengk_profile_refine",
@@ -173,6 +174,9 @@ def lib():
         L.pengk_mask_sites.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]
         L.pengk_pack_scan_sizes.argtypes = [vp, vp, vp, vp, u64, C.c_int, C.c_int, vp, vp, C.POINTER(PackedStruct)]
         L.pengk_pack_scan.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, C.c_int, vp, vp, vp, u64, vp, u64]
+        L.pengk_seq_strata.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, C.c_int, vp, vp]
+        L.pengk_match_quotas.argtypes = [vp, vp, u64, vp, C.POINTER(u64)]
+        L.pengk_select_strata.argtypes = [vp, vp, u64, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(u64)]
         L.pengk_motif_enrich.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp]
         L.pengk_hypergeom_log10_sf.argtypes = [u64, u64, u64, u64, C.POINTER(C.c_double)]
         L.pengk_enrich_summary.argtypes = [vp, vp, u64, C.c_int32, u64, u64, C.POINTER(EnrichmentStruct)]
@@ -319,6 +323,19 @@ def hypergeom_log10_sf(N, K, n, k):
     out = C.c_double()
     _check(lib().pengk_hypergeom_log10_sf(int(N), int(K), int(n), int(k), C.byref(out)))
     return out.value
+
+
+def match_quotas(h_in, h_ctrl, ratio=1):
+    """(quota, shortfall): how many control sequences of every stratum to keep for `ratio` per input sequence, from the
+    two stratum histograms of Context.seq_strata (256 uint64 each), and what the control could not supply
+    (pengk_match_quotas, CPU)"""
+    a = np.ascontiguousarray(h_in, np.uint64)
+    b = np.ascontiguousarray(h_ctrl, np.uint64)
+    assert a.shape == b.shape == (256,)
+    q = np.zeros(256, np.uint64)
+    short = C.c_uint64()
+    _check(lib().pengk_match_quotas(a.ctypes.data, b.ctypes.data, int(ratio), q.ctypes.data, C.byref(short)))
+    return q, int(short.value)
 
 
 def enrich_summary(pos_hist, neg_hist, thr, n_pos, n_neg):
@@ -761,6 +778,34 @@ class Context:
             self.set_sequences(words, items, st.n_words, st.n_items, st.W, st.item_windows, st.max_bin_bound, st.all_whole)
             self.set_option("n_windows_hint", st.n_windows)
         return words, items, st
+
+    # ---- a control set matched to the input (--score-negatives control) -------------------------------------
+    def seq_strata(self, scan, gc_bins=10, use_length=True, all_valid=False, stratum=None, hist=None, n_seq=None):
+        """(stratum, hist), both on the device: the stratum (length bin * gc_bins + GC bin, 0xFFFF without a valid base) of
+        every sequence of `scan` and the 256 stratum counts (pengk_seq_strata).  all_valid: d_valid = NULL.  hist: a device
+        array of 256 uint64 to ADD to instead of a fresh zeroed one.  n_seq: another count than scan[4] (argument tests)."""
+        if stratum is None:
+            stratum = self.empty(max(scan[4], 1), np.uint16)
+        if hist is None:
+            hist = self.to_device(np.zeros(256, np.uint64))
+        _check(lib().pengk_seq_strata(self.h, _ptr(scan[0]), None if all_valid else _ptr(scan[1]), _ptr(scan[2]), _ptr(scan[3]),
+                                      scan[4] if n_seq is None else n_seq, int(gc_bins), int(use_length), _ptr(stratum), _ptr(hist)))
+        return stratum, hist
+
+    def select_strata(self, stratum, n_seq, count, quota, rank0, offs, lens):
+        """(sel_offs, sel_lens, sel_index, n_sel): the kept sequences of this call's n_seq (their strata in `stratum`, device
+        uint16) as compacted device arrays -- with the words of the layout that offs / lens belong to, a scan layout of
+        n_sel sequences -- and their count (pengk_select_strata).  count / quota / rank0: 256 uint64 each, host."""
+        c = np.ascontiguousarray(count, np.uint64)
+        q = np.ascontiguousarray(quota, np.uint64)
+        r0 = np.ascontiguousarray(rank0, np.uint64)
+        assert c.shape == q.shape == r0.shape == (256,)
+        so, sl = self.empty(max(n_seq, 1), np.int64), self.empty(max(n_seq, 1), np.uint32)
+        si = self.empty(max(n_seq, 1), np.uint32)
+        n_sel = C.c_uint64()
+        _check(lib().pengk_select_strata(self.h, _ptr(stratum), n_seq, c.ctypes.data, q.ctypes.data, r0.ctypes.data, _ptr(offs),
+                                         _ptr(lens), _ptr(so), _ptr(sl), _ptr(si), C.byref(n_sel)))
+        return so, sl, si, int(n_sel.value)
 
     def sites_histograms(self, scan, S, lens, both, thr, hi, counts=None, hist=None, tests=None, offs=None):
         """(hists, tests): hists[m] (uint64, max(0, hi[m] - thr[m] + 1) bins) the sites of motif m by score - thr[m], tests[m]

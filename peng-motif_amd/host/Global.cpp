@@ -81,6 +81,16 @@ int Global::eraseRounds = 1;
 double Global::erasePvalue = 1e-4;
 bool Global::discriminative = false;
 double Global::discriminativePseudocount = 1.0;
+bool Global::scoreNegativesControl = false;
+bool Global::controlMatchGc = true;
+bool Global::controlMatchLength = true;
+int Global::controlMatchGcBins = 10;
+unsigned long long Global::controlRatio = 1;
+char* Global::controlMatchReportFilename = nullptr;
+
+namespace {
+void exit_log(const std::string& msg);  // (a logger line at level ERROR; below)
+}
 
 void Global::init(int nargs, char* args[]) {
   readArguments(nargs, args);
@@ -108,6 +118,11 @@ void Global::init(int nargs, char* args[]) {
   }
 }
 
+void Global::exitWithError(const std::string& msg) {
+  if (pengk_host::rank() == 0) exit_log(msg);
+  exit(4);
+}
+
 void Global::destruct() {
   if (backgroundSequenceSet != inputSequenceSet) delete backgroundSequenceSet;
   delete inputSequenceSet;
@@ -128,6 +143,7 @@ void log_line(const char* level, const std::string& msg) {
   fprintf(stderr, "- %s.%03ld %s: %s\n\n", clock, (long)tv.tv_usec / 1000, level, msg.c_str());
   fflush(stderr);
 }
+void exit_log(const std::string& msg) { log_line("ERROR", msg); }
 // value of an option that needs one; exits with 4 like the reference when it is missing
 const char* need(int& i, int nargs, char* args[], void (*help)()) {
   const char* opt = args[i];
@@ -254,8 +270,9 @@ void Global::readArguments(int nargs, char* args[]) {
       scoreSeed = std::stoull(need(i, nargs, args, printHelp));
     } else if (!strcmp(a, "--score-negatives")) {
       const char* v = need(i, nargs, args, printHelp);
-      if (!strcmp(v, "sampled")) scoreNegativesShuffled = false;
-      else if (!strcmp(v, "shuffled")) scoreNegativesShuffled = true;
+      if (!strcmp(v, "sampled")) scoreNegativesShuffled = scoreNegativesControl = false;
+      else if (!strcmp(v, "shuffled")) scoreNegativesShuffled = true, scoreNegativesControl = false;
+      else if (!strcmp(v, "control")) scoreNegativesShuffled = false, scoreNegativesControl = true;
       else {
         printHelp();
         log_line("ERROR", "Unknown expression following --score-negatives");
@@ -457,6 +474,39 @@ void Global::readArguments(int nargs, char* args[]) {
         log_line("ERROR", "--discriminative-pseudocount must be a finite number, 0 or above");
         exit(4);
       }
+    } else if (!strcmp(a, "--control-match")) {
+      const char* v = need(i, nargs, args, printHelp);
+      if (!strcmp(v, "gc,length") || !strcmp(v, "length,gc")) controlMatchGc = controlMatchLength = true;
+      else if (!strcmp(v, "gc")) controlMatchGc = true, controlMatchLength = false;
+      else if (!strcmp(v, "length")) controlMatchGc = false, controlMatchLength = true;
+      else if (!strcmp(v, "none")) controlMatchGc = controlMatchLength = false;
+      else {
+        printHelp();
+        log_line("ERROR", "Unknown expression following --control-match");
+        exit(4);
+      }
+    } else if (!strcmp(a, "--control-match-gc-bins")) {
+      const char* v = need(i, nargs, args, printHelp);
+      char* end = nullptr;
+      const long g = std::strtol(v, &end, 10);
+      if (end == v || *end || g < 1 || g > 16) {
+        printHelp();
+        log_line("ERROR", "--control-match-gc-bins must be an integer in 1..16");
+        exit(4);
+      }
+      controlMatchGcBins = (int)g;
+    } else if (!strcmp(a, "--control-ratio")) {
+      const char* v = need(i, nargs, args, printHelp);
+      char* end = nullptr;
+      const long long r = std::strtoll(v, &end, 10);
+      if (end == v || *end || r < 1 || r > 1000000) {
+        printHelp();
+        log_line("ERROR", "--control-ratio must be an integer in 1..1000000");
+        exit(4);
+      }
+      controlRatio = (unsigned long long)r;
+    } else if (!strcmp(a, "--control-match-report")) {
+      controlMatchReportFilename = (char*)need(i, nargs, args, printHelp);
     } else if (!strcmp(a, "--version")) {
       std::cout << "peng_motif " << VERSION_NUMBER << std::endl;  // (src/Global.cpp:299-301: without the word)
       exit(0);
@@ -470,6 +520,11 @@ void Global::readArguments(int nargs, char* args[]) {
   if (discriminative && !backgroundSequenceFilename) {
     printHelp();
     log_line("ERROR", "--discriminative requires --background-sequences (the control set)");
+    exit(4);
+  }
+  if (scoreNegativesControl && !backgroundSequenceFilename) {
+    printHelp();
+    log_line("ERROR", "--score-negatives control requires --background-sequences (the control set)");
     exit(4);
   }
   if (dinucModelsFilename && !dinucFilename) {
@@ -531,6 +586,13 @@ void Global::printHelp() {
   printf("  --score-negatives STRING       sampled: the negatives of --score-motifs come from the background model;\n");
   printf("                                 shuffled: every input sequence shuffled with its own dinucleotide counts\n");
   printf("                                 kept, for inputs of mixed composition (default sampled)\n");
+  printf("                                 control: the sequences of the --background-sequences file, drawn to match the\n");
+  printf("                                 input (--control-match); the seed has no effect then\n");
+  printf("  --control-match STRING         gc,length | gc | length | none: what the control sequences kept as negatives\n");
+  printf("                                 are matched to the input by (default gc,length; none: the whole control)\n");
+  printf("  --control-match-gc-bins INT    GC content bins of the match, 1..16 (default 10)\n");
+  printf("  --control-ratio INT            control sequences wanted per input sequence, 1 or above (default 1)\n");
+  printf("  --control-match-report FILE    write the match per stratum (TSV: length range, GC range, input, control, kept)\n");
   printf("  --sites FILE                   write every occurrence of the motifs (TSV: sequence, position, strand,\n");
   printf("                                 score, p-value) at p-value --sites-pvalue or below\n");
   printf("  --sites-pvalue FLOAT           p-value threshold of --sites, in (0, 1] (default 1e-4)\n");

@@ -97,9 +97,16 @@ class Global {
   static double erasePvalue;                 // --erase-pvalue
   static bool discriminative;                // --discriminative (new: the k-mer sweep held to the control set's counts)
   static double discriminativePseudocount;   // --discriminative-pseudocount
+  static bool scoreNegativesControl;         // --score-negatives control (new: the --background-sequences file as negatives, matched to the input)
+  static bool controlMatchGc;                // --control-match: gc,length | gc | length | none
+  static bool controlMatchLength;
+  static int controlMatchGcBins;             // --control-match-gc-bins, 1..16
+  static unsigned long long controlRatio;    // --control-ratio: control sequences per input sequence, 1 or above
+  static char* controlMatchReportFilename;   // --control-match-report
 
   static void init(int nargs, char* args[]);
   static void destruct();
+  static void exitWithError(const std::string& msg);  // a logger line (rank 0) and exit status 4, as for a bad flag
 
  private:
   static void readArguments(int nargs, char* args[]);

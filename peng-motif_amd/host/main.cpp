@@ -19,6 +19,7 @@
 #include "motif_dinuc.h"
 #include "motif_enrich.h"
 #include "motif_erase.h"
+#include "motif_match.h"
 #include "motif_refine.h"
 #include "motif_spacing.h"
 #include "motif_sites.h"
@@ -130,8 +131,19 @@ int main(int nargs, char** args) {
     clock.lap("erase rounds");
   }
   // (--enrich scores against the negatives of --score-motifs and --dinuc: with it they are built once, for all three)
+  // (--score-negatives control: the control set, matched to the input, serves whichever of the three is asked for)
   std::unique_ptr<Negatives> negatives;
-  if (Global::enrichFilename) {
+  if (Global::scoreNegativesControl && (Global::scoreMotifs || Global::dinucFilename || Global::enrichFilename)) {
+    negatives.reset(new Negatives);
+    MatchSettings ms;
+    ms.gc = Global::controlMatchGc;
+    ms.length = Global::controlMatchLength;
+    ms.gc_bins = Global::controlMatchGcBins;
+    ms.ratio = Global::controlRatio;
+    if (Global::controlMatchReportFilename) ms.report_path = Global::controlMatchReportFilename;
+    build_control_negatives(*Global::backgroundSequenceSet, *scan, ms, negatives.get());
+    clock.lap("control negatives");
+  } else if (Global::enrichFilename) {
     negatives.reset(new Negatives);
     build_negatives(*Global::inputSequenceSet, *scan, *bgModel, Global::bgModelOrder, Global::scoreSeed,
                     Global::scoreNegativesShuffled, negatives.get());

@@ -53,7 +53,8 @@ void write_motif_dinuc(const std::vector<IUPACPattern*>& pats, SequenceSet& set,
   pengk_ctx* ctx = pengk_host::context();
   const bool device = n_motifs && n_local;
   std::vector<long long> counts((size_t)n_motifs * (B1 + B2), 0);
-  DeviceBuffer<int32_t> d_best((size_t)std::max(n_motifs, 1) * std::max<size_t>(n_local, 1));
+  const size_t n_neg = shared ? shared->n(in) : n_local;  // (a control set brings its own number of sequences)
+  DeviceBuffer<int32_t> d_best((size_t)std::max(n_motifs, 1) * std::max<size_t>(std::max(n_local, n_neg), 1));
   if (device) {
     DeviceBuffer<uint64_t> d_site((size_t)n_motifs * n_local);
     DeviceBuffer<uint64_t> d_counts(counts.size());
@@ -124,10 +125,10 @@ void write_motif_dinuc(const std::vector<IUPACPattern*>& pats, SequenceSet& set,
           "pengk_motif_scan_dinuc");
     check(pengk_score_histograms(ctx, n_motifs, d_best.get(), n_local, lo.data(), hi.data(), hoffs.data(), d_hist.get()),
           "pengk_score_histograms");
-    check(pengk_motif_scan_dinuc(ctx, neg.d_words.get(), neg.valid_or_null(), in.d_offs.get(), in.d_lens.get(), n_local,
-                                 n_motifs, S0.data(), D[k].data(), wide.data(), both, d_best.get()),
+    check(pengk_motif_scan_dinuc(ctx, neg.words(), neg.valid_or_null(), neg.offs(in), neg.lens(in), n_neg, n_motifs, S0.data(),
+                                 D[k].data(), wide.data(), both, d_best.get()),
           "pengk_motif_scan_dinuc");
-    check(pengk_score_histograms(ctx, n_motifs, d_best.get(), n_local, lo.data(), hi.data(), hoffs.data(), d_hist.get() + nh),
+    check(pengk_score_histograms(ctx, n_motifs, d_best.get(), n_neg, lo.data(), hi.data(), hoffs.data(), d_hist.get() + nh),
           "pengk_score_histograms");
     std::vector<long long> hist(2 * nh);
     d_hist.download((uint64_t*)hist.data(), 2 * nh);

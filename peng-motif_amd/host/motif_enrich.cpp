@@ -50,7 +50,8 @@ void write_motif_enrich(const std::vector<MemeMotif>& db, const ScanInput& in, N
   // per set: the motifs' bins, then their scored counters
   const uint64_t nh = hoffs[n_db], per_set = nh + (uint64_t)n_db;
   std::vector<uint64_t> hist(std::max<uint64_t>(2 * per_set, 1), 0);
-  if (n_db && n_local) {
+  const size_t n_neg = neg.n(in);  // (a control set brings its own number of sequences)
+  if (n_db && (n_local || n_neg)) {
     pengk_ctx* ctx = pengk_host::context();
     DeviceBuffer<uint64_t> d_hist(2 * per_set);
     check(pengk_memset(ctx, d_hist.get(), 0, 2 * per_set * sizeof(uint64_t)), "pengk_memset");
@@ -58,9 +59,8 @@ void write_motif_enrich(const std::vector<MemeMotif>& db, const ScanInput& in, N
     check(pengk_motif_enrich(ctx, in.d_words.get(), in.d_valid.get(), in.d_offs.get(), in.d_lens.get(), n_local, n_db, S.data(),
                              len.data(), both, thr.data(), hi.data(), hoffs.data(), d_hist.get(), d_hist.get() + nh),
           "pengk_motif_enrich");
-    check(pengk_motif_enrich(ctx, neg.d_words.get(), neg.valid_or_null(), in.d_offs.get(), in.d_lens.get(), n_local, n_db,
-                             S.data(), len.data(), both, thr.data(), hi.data(), hoffs.data(), d_hist.get() + per_set,
-                             d_hist.get() + per_set + nh),
+    check(pengk_motif_enrich(ctx, neg.words(), neg.valid_or_null(), neg.offs(in), neg.lens(in), n_neg, n_db, S.data(), len.data(),
+                             both, thr.data(), hi.data(), hoffs.data(), d_hist.get() + per_set, d_hist.get() + per_set + nh),
           "pengk_motif_enrich");
     d_hist.download(hist.data(), 2 * per_set);
   }

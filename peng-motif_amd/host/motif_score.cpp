@@ -143,7 +143,8 @@ std::vector<MotifScore> score_motifs(const std::vector<IUPACPattern*>& pats, Seq
   }
   const uint64_t nh = std::max<uint64_t>(hoffs[n_motifs], 1);
   DeviceBuffer<uint64_t> d_hist(2 * nh);
-  DeviceBuffer<int32_t> d_best((size_t)std::max(n_motifs, 1) * std::max<size_t>(n_local, 1));
+  const size_t n_neg = shared ? shared->n(in) : n_local;  // (a control set brings its own number of sequences)
+  DeviceBuffer<int32_t> d_best((size_t)std::max(n_motifs, 1) * std::max<size_t>(std::max(n_local, n_neg), 1));
   pengk_ctx* ctx = pengk_host::context();
   check(pengk_memset(ctx, d_hist.get(), 0, 2 * nh * sizeof(uint64_t)), "pengk_memset");
   const int both = both_strands ? 1 : 0;
@@ -155,14 +156,14 @@ std::vector<MotifScore> score_motifs(const std::vector<IUPACPattern*>& pats, Seq
   Negatives own;
   if (!shared) build_negatives(set, in, bg, K, seed, shuffled, &own);
   Negatives& neg = shared ? *shared : own;
-  check(pengk_motif_scan(ctx, neg.d_words.get(), neg.valid_or_null(), in.d_offs.get(), in.d_lens.get(), n_local, n_motifs,
-                         S.data(), len.data(), both, d_best.get()),
+  check(pengk_motif_scan(ctx, neg.words(), neg.valid_or_null(), neg.offs(in), neg.lens(in), n_neg, n_motifs, S.data(), len.data(),
+                         both, d_best.get()),
         "pengk_motif_scan");
-  check(pengk_score_histograms(ctx, n_motifs, d_best.get(), n_local, lo.data(), hi.data(), hoffs.data(), d_hist.get() + nh),
+  check(pengk_score_histograms(ctx, n_motifs, d_best.get(), n_neg, lo.data(), hi.data(), hoffs.data(), d_hist.get() + nh),
         "pengk_score_histograms");
   std::vector<long long> hist(2 * nh);
   d_hist.download((uint64_t*)hist.data(), 2 * nh);
-  lap(shuffled ? "shuffle + scan + histograms" : "sample + scan + histograms");
+  lap(neg.control ? "scan + histograms" : shuffled ? "shuffle + scan + histograms" : "sample + scan + histograms");
   SequenceSet::allreduceSum(hist.data(), hist.size());  // (integers: the ranks' sum is exact)
   for (int m = 0; m < n_motifs; ++m)
     check(pengk_score_summary((const uint64_t*)hist.data() + hoffs[m], (const uint64_t*)hist.data() + nh + hoffs[m],

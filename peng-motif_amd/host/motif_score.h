@@ -6,6 +6,7 @@
 #define PENGK_HOST_MOTIF_SCORE_H_
 
 #include <cstdint>
+#include <memory>
 #include <vector>
 
 #include "iupac_pattern.h"
@@ -37,11 +38,27 @@ void motif_log_odds(const std::vector<IUPACPattern*>& pats, const float* bg0, st
 // ones): sampled from the background model of order K (V from bg) at the records' global indices, or, shuffled, every
 // sequence's own dinucleotide-preserving shuffle with validity words of its own (valid_or_null(): NULL for a sample,
 // whose bases are all valid).
+// Or, --score-negatives control (motif_match.h), real sequences: the control set's own scan layout, and -- unless the
+// whole control is used -- the compacted offsets / lengths of the sequences kept of it.  The consumers scan
+// words() / valid_or_null() over offs(in) / lens(in) / n(in) and size what they keep per sequence by the larger count.
 struct Negatives {
   pengk_host::DeviceBuffer<uint64_t> d_words;
   pengk_host::DeviceBuffer<uint32_t> d_valid;
   bool shuffled = false;
-  const uint32_t* valid_or_null() { return shuffled ? d_valid.get() : nullptr; }
+  std::unique_ptr<ScanInput> control;             // the control set (this rank's records)
+  bool selected = false;                          // d_sel_offs / d_sel_lens / n_sel hold the kept ones
+  pengk_host::DeviceBuffer<int64_t> d_sel_offs;
+  pengk_host::DeviceBuffer<uint32_t> d_sel_lens;
+  size_t n_sel = 0;
+  const uint64_t* words() const { return control ? control->d_words.get() : d_words.get(); }
+  const uint32_t* valid_or_null() const { return control ? control->d_valid.get() : shuffled ? d_valid.get() : nullptr; }
+  const int64_t* offs(const ScanInput& in) const {
+    return !control ? in.d_offs.get() : selected ? d_sel_offs.get() : control->d_offs.get();
+  }
+  const uint32_t* lens(const ScanInput& in) const {
+    return !control ? in.d_lens.get() : selected ? d_sel_lens.get() : control->d_lens.get();
+  }
+  size_t n(const ScanInput& in) const { return !control ? in.n_local : selected ? n_sel : control->n_local; }
 };
 void build_negatives(SequenceSet& set, const ScanInput& in, BackgroundModel& bg, int K, uint64_t seed, bool shuffled,
                      Negatives* out);
