@@ -129,6 +129,57 @@ def scenario(seed, n_in=2000, n_ctrl=6000):
     return pos, ctrl
 
 
+# ---- the scenario of the match modes -----------------------------------------------------------------------------------------
+EDGE_LENGTHS = [30, 47, 48, 6143, 6144, 7000]  # length bins 0, 0 | 1, 14 | 15, 15: both ends of the half-octave scale
+EDGE_SEED = 98  # (the edge sequences have a generator of their own: scenario(seed) stays what it is)
+
+# (name, the CLI's flags, match by GC, match by length, G, ratio)
+MODES = [
+    ("default", [], True, True, 10, 1),
+    ("gc4_r3", ["--control-match", "gc", "--control-match-gc-bins", "4", "--control-ratio", "3"], True, False, 4, 3),
+    ("length_r2", ["--control-match", "length", "--control-ratio", "2"], False, True, 1, 2),
+    ("both16_r3", ["--control-match-gc-bins", "16", "--control-ratio", "3"], True, True, 16, 3),
+    ("gc1", ["--control-match", "gc", "--control-match-gc-bins", "1"], True, False, 1, 1),
+]
+
+
+def mode_scenario(seed):
+    """(input, control): scenario(seed) and, behind it, sequences of the lengths at which the length bins begin and end
+    (EDGE_LENGTHS) at 60 % GC -- three of each in the input, then two of each in the control"""
+    pos, ctrl = scenario(seed)
+    rng = np.random.default_rng(EDGE_SEED + seed)
+    pos = pos + [c for L in EDGE_LENGTHS for c in draw(rng, 3, L, 0.60)]
+    ctrl = ctrl + [c for L in EDGE_LENGTHS for c in draw(rng, 2, L, 0.60)]
+    return pos, ctrl
+
+
+def match(pos, ctrl, gc=True, length=True, G=10, ratio=1):
+    """what the CLI does with one mode: a dict of h_in, h_ctrl, quota, short, kept (indices into ctrl) and in_use.
+    Without GC matching there is one GC bin, whatever --control-match-gc-bins says."""
+    G = G if gc else 1
+    _, h_in = strata(pos, G, length)
+    s_ctrl, h_ctrl = strata(ctrl, G, length)
+    quota, short = quotas(h_in, h_ctrl, ratio)
+    return dict(h_in=h_in, h_ctrl=h_ctrl, quota=quota, short=short, kept=select(s_ctrl, h_ctrl, quota),
+                in_use=int((h_in > 0).sum()), G=G, use_length=length, ratio=ratio)
+
+
+def stdout_line(name, m, n_ctrl):
+    """the CLI's line on stdout for the mode `name` ("gc,length", "gc" or "length") and the result m of match()"""
+    return "control negatives: matched by %s (%d GC bin%s, ratio %d): %d strat%s in use, kept %d of %d control sequences, shortfall %d" % (
+        name, m["G"], "" if m["G"] == 1 else "s", m["ratio"], m["in_use"], "um" if m["in_use"] == 1 else "a", len(m["kept"]),
+        n_ctrl, m["short"])
+
+
+def front_loaded(ctrl, h_in, G=10, use_length=True):
+    """(the control reordered, n): the n sequences of a stratum the input uses first, the others behind them, each group
+    in its old order.  Read by several ranks (byte ranges), the later ranks' shards then hold nothing to keep."""
+    s, _ = strata(ctrl, G, use_length)
+    used = (s < N_STRATA) & (np.asarray(h_in)[np.minimum(s, N_STRATA - 1)] > 0)
+    order = np.concatenate([np.flatnonzero(used), np.flatnonzero(~used)])
+    return [ctrl[i] for i in order], int(used.sum())
+
+
 def word_pwm(word, p=0.85):
     """a PWM (w x 4) with probability p on the word's letter of every column"""
     out = np.full((len(word), 4), (1 - p) / 3)

@@ -285,12 +285,13 @@ def mafk_model_inputs(fa):
     return seqs, negs, V
 
 
-def assert_files_equal_the_model(fa, js, report, models, both, pvalue=1e-4, flank=0, alpha=20.0):
+def assert_files_equal_the_model(inputs, js, report, models, both, pvalue=1e-4, flank=0, alpha=20.0, batch=True):
     """byte for byte: every motif's report line and models block against the model run from the log-odds the run scanned
     with (found_log_odds of tests/test_gpu_motif_refine.py; where an entry of them is ambiguous, against the model of one
     of its possible values -- at most 64 per motif, more fails the test).  From the counts on the run and the model hold
-    the same integers."""
-    seqs, negs, V = mafk_model_inputs(fa)
+    the same integers.  inputs: (the input's sequences, the negatives, the background model V of orders 0..2), as
+    mafk_model_inputs gives them for a FASTA file and sampled negatives; batch: the model's vectorised path."""
+    seqs, negs, V = inputs
     pats = json.loads(js)["patterns"]
     lines = report.splitlines(True)
     assert lines[0] == md.REPORT_HEAD and len(lines) == 1 + len(pats)
@@ -306,10 +307,10 @@ def assert_files_equal_the_model(fa, js, report, models, both, pvalue=1e-4, flan
             S1 = S.copy()
             for (idx, _), val in zip(amb, pick):
                 S1[idx] = val
-            k = md.site_counts(seqs, S1, m, both, pvalue, flank, V[0], batch=True)
+            k = md.site_counts(seqs, S1, m, both, pvalue, flank, V[0], batch=batch)
             key = k[0].tobytes() + k[1].tobytes()
             if key not in seen:
-                seen[key] = md.analyse(seqs, negs, S1, m, V[0], V[1], both, pvalue, flank, alpha, batch=True, counts=k)
+                seen[key] = md.analyse(seqs, negs, S1, m, V[0], V[1], both, pvalue, flank, alpha, batch=batch, counts=k)
             r = seen[key]
             want.append((md.report_line(p["iupac_motif"], m + 1, r), md.models_block(p["iupac_motif"], r)))
         assert (lines[1 + m], blocks[m]) in want, (m, lines[1 + m], want[0][0])
@@ -330,7 +331,7 @@ def test_cli_dinuc_equals_the_model_and_leaves_everything_else_alone(tmp_path):
     for ext, got in [("stdout", so), ("meme", meme), ("json", js)]:
         with open(os.path.join(GOLD, "cli", "cli_mafk_w10." + ext), "rb") as fh:
             assert got == fh.read(), ext
-    assert_files_equal_the_model(fa, js, rep.read_text(), mod.read_text(), True)
+    assert_files_equal_the_model(mafk_model_inputs(fa), js, rep.read_text(), mod.read_text(), True)
     rows = report_rows(rep.read_text())
     assert rows[0]["motif"] == "CTGASTCAGCAAW" and rows[0]["index"] == "1" and rows[0]["width"] == "13" and rows[0]["flank"] == "0"
     assert int(rows[0]["sites"]) > 100 and 0.5 < float(rows[0]["auc_order0"]) < 1 and 1 <= int(rows[0]["mi_max_pair"]) - 1 < 13
@@ -341,7 +342,7 @@ def test_cli_dinuc_equals_the_model_and_leaves_everything_else_alone(tmp_path):
     rc, so2, se, meme2, js2 = run_plain([fa, "-w", "10", "--dinuc", str(rep2), "--dinuc-models", str(mod2)] + args, tmp_path, tag="dn2")
     assert rc == 0, se.decode()[-2000:]
     assert (so2, meme2, js2) == (so, meme, js)
-    assert_files_equal_the_model(fa, js2, rep2.read_text(), mod2.read_text(), True, 1e-5, 3, 5.0)
+    assert_files_equal_the_model(mafk_model_inputs(fa), js2, rep2.read_text(), mod2.read_text(), True, 1e-5, 3, 5.0)
     rows2 = report_rows(rep2.read_text())
     assert rows2[0]["width"] == "19" and rows2[0]["flank"] == "3" and int(rows2[0]["sites"]) < int(rows[0]["sites"])
     assert mod2.read_text().startswith("# first-order motif models: alpha= 5 bg_order= 1\n")
@@ -356,7 +357,7 @@ def test_cli_dinuc_plus_strand(tmp_path):
     rep, mod = tmp_path / "plus.tsv", tmp_path / "plus.models"
     rc, _, se, _, js = run_plain([fa, "-w", "10", "--strand", "PLUS", "--dinuc", str(rep), "--dinuc-models", str(mod)], tmp_path)
     assert rc == 0, se.decode()[-2000:]
-    assert_files_equal_the_model(fa, js, rep.read_text(), mod.read_text(), False)
+    assert_files_equal_the_model(mafk_model_inputs(fa), js, rep.read_text(), mod.read_text(), False)
 
 
 def test_cli_shuffled_negatives_change_the_aucs_and_nothing_else(tmp_path):
