@@ -555,6 +555,29 @@ int pengk_pack_scan(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_v
                     const uint32_t* d_lens, uint64_t n_seq, int W, int item_windows, const uint64_t* d_seq_base,
                     const uint64_t* d_seq_item, uint64_t* d_out_words, uint64_t n_words, uint64_t* d_out_items, uint64_t n_items);
 
+/* ---- masking low-complexity stretches (--mask-low-complexity: poly-A tracts, (CA)n and their like are taken out of the
+ *      input before anything is counted, as dustmasker, sdust and RepeatMasker's simple-repeat pass do in front of other
+ *      discovery tools) ------------------------------------------------------------------------------
+ * This project's own statement of the symmetric DUST criterion of Morgulis et al. 2006, integer throughout: a numpy
+ * restatement and any sharding give the same bits.  The numbers are NOT promised to be those of NCBI's dustmasker or of
+ * sdust.  Per sequence of the scan layout above, letters s[0..L) and validity bits v (d_valid = NULL: every base valid):
+ *   triplet   one stands at p (0 <= p <= L-3) iff v[p] & v[p+1] & v[p+2]; its value t[p] = 16 s[p] + 4 s[p+1] + s[p+2]
+ *   interval  (i, l) = the triplets i .. i+l-1, all standing, 2 <= l <= PENGK_DUST_WINDOW - 2: at most 64 bases
+ *   score     num(i, l) / (l - 1), num(i, l) = sum over the triplet values x of c_x (c_x - 1) / 2, c_x the occurrences of
+ *             x in the interval; fractions are compared by cross-multiplication (num <= 1891: 32 bits hold every product)
+ *   high      10 * num > threshold * (l - 1)
+ *   perfect   high, and no interval (i', l') inside it, l' >= 2, has a strictly larger score (equality keeps it perfect)
+ *   cover     the bases [i, i + l + 2) of every perfect interval
+ * d_out_valid (the layout of d_valid, must differ from it) receives v & ~cover for every word of every sequence, the bits
+ * at and beyond a sequence's end cleared, as pengk_mask_sites leaves them.  d_masked[0] / d_masked[1] (uint64) are ADDED to
+ * (caller-zeroed; shards and several calls sum exactly): the bits that went from 1 to 0 and the sequences that lost at
+ * least one.  n_seq = 0 does nothing.  PENGK_ERR_ARG: threshold outside 1 .. 1000 (DUST's is 20; above 310 nothing can
+ * be high, which is legal), n_seq >= 2^32, d_out_valid == d_valid.  Asynchronous on the context's stream. */
+#define PENGK_DUST_WINDOW 64
+int pengk_mask_low_complexity(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_valid, const int64_t* d_offs,
+                              const uint32_t* d_lens, uint64_t n_seq, int threshold, uint32_t* d_out_valid,
+                              uint64_t* d_masked /* [2], ADDED to: bits that went 1 -> 0; sequences with at least one */);
+
 /* ---- a control set matched to the input (--score-negatives control: the negatives of the scoring steps are real
  *      sequences, drawn from the control in proportion to the input's GC content and length, as HOMER and BiasAway
  *      match theirs; this project's own definitions) -------------------------------------------------

@@ -36,7 +36,7 @@ EXPORTS = [
     "pengk_motif_scan", "pengk_score_histograms", "pengk_score_summary",
     "pengk_score_tail_pvalues", "pengk_score_threshold", "pengk_sites_count", "pengk_sites_slices", "pengk_sites_emit",
     "pengk_sites_histograms", "pengk_sites_qvalues", "pengk_qvalue_threshold",
-    "pengk_mask_sites", "pengk_pack_scan_sizes", "pengk_pack_scan",
+    "pengk_mask_sites", "pengk_pack_scan_sizes", "pengk_pack_scan", "pengk_mask_low_complexity",
     "pengk_seq_strata", "pengk_match_quotas", "pengk_select_strata",
     "pengk_motif_enrich", "pengk_hypergeom_log10_sf", "pengk_enrich_summary",
     "pengk_motif_best_sites", "pengk_centrality_histograms", "pengk_centrality_summary", "pengk_binomial_log10_sf",
@@ -172,6 +172,7 @@ def lib():
         L.pengk_sites_histograms.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
         L.pengk_sites_qvalues.argtypes = [vp, u64, u64, vp, vp]
         L.pengk_mask_sites.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]
+        L.pengk_mask_low_complexity.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, vp, vp]
         L.pengk_pack_scan_sizes.argtypes = [vp, vp, vp, vp, u64, C.c_int, C.c_int, vp, vp, C.POINTER(PackedStruct)]
         L.pengk_pack_scan.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, C.c_int, vp, vp, vp, u64, vp, u64]
         L.pengk_seq_strata.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, C.c_int, vp, vp]
@@ -759,6 +760,21 @@ class Context:
                                       scan[4], n, Sp.ctypes.data, ln.ctypes.data, int(both), th.ctypes.data, _ptr(out_valid),
                                       _ptr(sites), _ptr(erased)))
         return out_valid, sites, erased
+
+    # ---- masking low-complexity stretches (--mask-low-complexity) ---------------------------------------------
+    def mask_low_complexity(self, scan, threshold=20, all_valid=False, out_valid=None, masked=None, n_seq=None):
+        """(out_valid, masked), both on the device: the validity words of `scan` with the cover of its perfect intervals
+        cleared (pengk_mask_low_complexity) and the two counts -- bits cleared, sequences that lost one.  all_valid:
+        d_valid = NULL.  masked: a device array of 2 uint64 to ADD to instead of a fresh zeroed one.  n_seq: another count
+        than scan[4] (argument tests)."""
+        if out_valid is None:
+            out_valid = self.empty(scan[0].shape, np.uint32)
+        if masked is None:
+            masked = self.to_device(np.zeros(2, np.uint64))
+        _check(lib().pengk_mask_low_complexity(self.h, _ptr(scan[0]), None if all_valid else _ptr(scan[1]), _ptr(scan[2]),
+                                               _ptr(scan[3]), scan[4] if n_seq is None else n_seq, int(threshold),
+                                               _ptr(out_valid), _ptr(masked)))
+        return out_valid, masked
 
     def pack_scan(self, scan, W, item_windows=0, valid=None, all_valid=False, attach=False):
         """the sequences of `scan` (under the validity words `valid` instead of its own, when given) in the count layout,

@@ -79,6 +79,9 @@ int Global::spacingMotifs = 16;
 char* Global::eraseFilename = nullptr;
 int Global::eraseRounds = 1;
 double Global::erasePvalue = 1e-4;
+bool Global::maskLowComplexity = false;
+int Global::maskThreshold = 20;
+char* Global::maskReportFilename = nullptr;
 bool Global::discriminative = false;
 double Global::discriminativePseudocount = 1.0;
 bool Global::scoreNegativesControl = false;
@@ -102,7 +105,7 @@ void Global::init(int nargs, char* args[]) {
   // (the scoring, the sites, the centrality, the refinement, the spacing, the first-order models and the database
   // enrichment scan the input after the motifs are found)
   pengk_host::keep_host_codes(scoreMotifs || sitesFilename || centralityFilename || refineFilename || spacingFilename ||
-                              dinucFilename || enrichFilename || eraseFilename);
+                              dinucFilename || enrichFilename || eraseFilename || maskLowComplexity);
   // both strands are handled inside the count; sequences are always read single stranded
   // ... and every chunk of the input set is packed and sent to the device while the rest is still being read
   pengk_host::begin_streaming_pack(patternLength);
@@ -189,6 +192,7 @@ void Global::readArguments(int nargs, char* args[]) {
     exit(-1);
   }
   inputSequenceFilename = args[1];
+  const char* mask_option = nullptr;  // the last option given that only means something with --mask-low-complexity
   for (int i = 2; i < nargs; i++) {
     const char* a = args[i];
     if (!strcmp(a, "-w")) {
@@ -463,6 +467,22 @@ void Global::readArguments(int nargs, char* args[]) {
         log_line("ERROR", "--erase-pvalue must be a number in (0, 1]");
         exit(4);
       }
+    } else if (!strcmp(a, "--mask-low-complexity")) {
+      maskLowComplexity = true;
+    } else if (!strcmp(a, "--mask-threshold")) {
+      const char* v = need(i, nargs, args, printHelp);
+      char* end = nullptr;
+      const long n = std::strtol(v, &end, 10);
+      if (end == v || *end || n < 1 || n > 1000) {
+        printHelp();
+        log_line("ERROR", "--mask-threshold must be an integer in [1, 1000]");
+        exit(4);
+      }
+      maskThreshold = (int)n;
+      mask_option = "--mask-threshold";
+    } else if (!strcmp(a, "--mask-report")) {
+      maskReportFilename = (char*)need(i, nargs, args, printHelp);
+      mask_option = "--mask-report";
     } else if (!strcmp(a, "--discriminative")) {
       discriminative = true;
     } else if (!strcmp(a, "--discriminative-pseudocount")) {
@@ -517,6 +537,11 @@ void Global::readArguments(int nargs, char* args[]) {
       if (pengk_host::rank() == 0) log_line("WARNING", std::string("Ignoring unknown option ") + a);
     }
   }
+  if (mask_option && !maskLowComplexity) {
+    printHelp();
+    log_line("ERROR", std::string(mask_option) + " requires --mask-low-complexity");
+    exit(4);
+  }
   if (discriminative && !backgroundSequenceFilename) {
     printHelp();
     log_line("ERROR", "--discriminative requires --background-sequences (the control set)");
@@ -556,6 +581,12 @@ void Global::printHelp() {
   printf("                                 well: the expected count of a k-mer is the larger of what the background\n");
   printf("                                 model predicts and what that control set shows (requires --background-sequences)\n");
   printf("  --discriminative-pseudocount FLOAT   added to every control count, 0 or above (default 1)\n");
+  printf("  --mask-low-complexity          mask low-complexity stretches (poly-A, (CA)n, triplet repeats) of the input on the\n");
+  printf("                                 device before anything is counted: this program's statement of the symmetric DUST\n");
+  printf("                                 criterion, window 64.  With --discriminative the control set is masked likewise;\n");
+  printf("                                 the rounds of --erase start from the masked input; the reports scan the input as it is\n");
+  printf("  --mask-threshold INT           score threshold of --mask-low-complexity, 1..1000 (default 20, DUST's)\n");
+  printf("  --mask-report FILE             the masked runs: sequence index, start, end (half-open), tab-separated\n");
   printf("  --erase FILE                   after the search, mask the sites of the motifs found and search what is left\n");
   printf("                                 again; the later rounds' motifs are appended.  FILE: one line per round and motif\n");
   printf("  --erase-rounds INT             further rounds of --erase, 1..8 (default 1); a round that finds or erases\n");

@@ -95,6 +95,9 @@ class Global {
   static char* eraseFilename;                // --erase (new: mask the found motifs' sites and search again)
   static int eraseRounds;                    // --erase-rounds: further rounds, 1..8
   static double erasePvalue;                 // --erase-pvalue
+  static bool maskLowComplexity;             // --mask-low-complexity (new: symmetric-DUST masking in front of round 1)
+  static int maskThreshold;                  // --mask-threshold: 1..1000 (DUST's 20)
+  static char* maskReportFilename;           // --mask-report: the masked runs, BED-like
   static bool discriminative;                // --discriminative (new: the k-mer sweep held to the control set's counts)
   static double discriminativePseudocount;   // --discriminative-pseudocount
   static bool scoreNegativesControl;         // --score-negatives control (new: the --background-sequences file as negatives, matched to the input)

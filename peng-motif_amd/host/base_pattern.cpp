@@ -47,17 +47,25 @@ BasePattern::BasePattern(const size_t pattern_length, Strand s, const int k, con
   if (discriminative) {
     SequenceSet* control = Global::backgroundSequenceSet;
     pengk_host::DeviceBuffer<uint64_t> d_cwords, d_citems;
-    pengk_packed pk;
-    check(pengk_pack(control->codes(), control->offsets(), (int64_t)control->getLocalN(), W, 0, &pk), "pengk_pack");
-    d_cwords.resize(pk.n_words);
-    d_citems.resize(pk.n_items + 1);
-    d_cwords.upload(pk.words, pk.n_words);
-    if (pk.n_items) d_citems.upload(pk.items, pk.n_items);
-    check(pengk_set_sequences(context(), d_cwords.get(), pk.n_words, d_citems.get(), pk.n_items, W, pk.item_windows,
-                              pk.max_bin_bound, pk.all_whole),
-          "pengk_set_sequences");
-    check(pengk_set_option(context(), "n_windows_hint", (int64_t)pk.n_windows), "pengk_set_option");
-    pengk_packed_free(&pk);
+    if (const pengk_host::PackedInput* cin = pengk_host::packed_input(control, W)) {
+      // --mask-low-complexity: the control behind the same mask as the input, packed on the device (host/motif_dust.cpp)
+      check(pengk_set_sequences(context(), cin->d_words, cin->n_words, cin->d_items, cin->n_items, W, cin->item_windows,
+                                cin->max_bin_bound, cin->all_whole),
+            "pengk_set_sequences");
+      check(pengk_set_option(context(), "n_windows_hint", (int64_t)cin->n_windows), "pengk_set_option");
+    } else {
+      pengk_packed pk;
+      check(pengk_pack(control->codes(), control->offsets(), (int64_t)control->getLocalN(), W, 0, &pk), "pengk_pack");
+      d_cwords.resize(pk.n_words);
+      d_citems.resize(pk.n_items + 1);
+      d_cwords.upload(pk.words, pk.n_words);
+      if (pk.n_items) d_citems.upload(pk.items, pk.n_items);
+      check(pengk_set_sequences(context(), d_cwords.get(), pk.n_words, d_citems.get(), pk.n_items, W, pk.item_windows,
+                                pk.max_bin_bound, pk.all_whole),
+            "pengk_set_sequences");
+      check(pengk_set_option(context(), "n_windows_hint", (int64_t)pk.n_windows), "pengk_set_option");
+      pengk_packed_free(&pk);
+    }
     d_ctrl_counts.resize(NP);
     check(pengk_count(context(), both, d_ctrl_counts.get(), d_ctrl_ltot.get()), "pengk_count");
     if (pengk_host::launched()) {

@@ -365,11 +365,18 @@ void override_packed_input(SequenceSet* set, const PackedInput* in) {
   g_override_set = in ? set : nullptr;
   g_override = in;
 }
+static SequenceSet* g_control_set = nullptr;
+static const PackedInput* g_control = nullptr;
+void override_control_input(SequenceSet* set, const PackedInput* in) {
+  g_control_set = in ? set : nullptr;
+  g_control = in;
+}
 void set_dump_subdir(const std::string& sub) { g_dump_subdir = sub; }
 const std::string& dump_subdir() { return g_dump_subdir; }
 
 const PackedInput* packed_input(SequenceSet* set, int W) {
   if (g_override && g_override_set == set && g_override->W == W) return g_override;
+  if (g_control && g_control_set == set && g_control->W == W) return g_control;
   Stream* st = g_stream;
   return st && st->set == set && st->in.W == W && st->in.d_words ? &st->in : nullptr;
 }

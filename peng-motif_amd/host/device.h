@@ -55,6 +55,9 @@ const PackedInput* packed_input(::SequenceSet* set, int W);      // of a set tha
 // --erase: from now on packed_input(set, W) hands out `in` (a masked copy of the set, packed on the device; the caller
 // owns it and its buffers) instead of what was packed during the read; nullptr ends that
 void override_packed_input(::SequenceSet* set, const PackedInput* in);
+// --mask-low-complexity with --discriminative: a second slot, for the control set (its masked copy, packed on the
+// device), which the rounds of --erase leave alone; nullptr ends that.  Empty without the flag.
+void override_control_input(::SequenceSet* set, const PackedInput* in);
 // PENGK_DUMP_TABLES: the folder below the one it names that BasePattern writes into ("" = that folder itself)
 void set_dump_subdir(const std::string& sub);
 const std::string& dump_subdir();

@@ -17,6 +17,7 @@
 #include "motif_centrality.h"
 #include "motif_compare.h"
 #include "motif_dinuc.h"
+#include "motif_dust.h"
 #include "motif_enrich.h"
 #include "motif_erase.h"
 #include "motif_match.h"
@@ -85,6 +86,21 @@ int main(int nargs, char** args) {
              : new BackgroundModel(*Global::backgroundSequenceSet, bg_model_order, Global::bgModelAlpha, Global::interpolateBG);
 
   clock.lap("background model");
+  // (the masking, the erasing, the scoring, the sites, the centrality, the refinement, the spacing, the first-order models
+  // and the database enrichment share one scan layout of the input)
+  std::unique_ptr<ScanInput> scan;
+  // --mask-low-complexity: round 1 (and with --discriminative its control count) sees the input behind the mask; the
+  // background model above and every report below see the input as it is
+  LowComplexityMask lc_mask;
+  // (a pattern length outside the supported range skips the mask without a word: Peng::process ends such a run with the
+  // reference's message a few lines below, as without the flag)
+  if (Global::maskLowComplexity && Global::patternLength >= PENGK_MIN_W && Global::patternLength <= PENGK_MAX_W) {
+    scan.reset(new ScanInput);
+    build_scan_input(*Global::inputSequenceSet, scan.get());
+    mask_low_complexity(*Global::inputSequenceSet, *scan, Global::discriminative ? Global::backgroundSequenceSet : nullptr,
+                        Global::patternLength, Global::maskThreshold, Global::maskReportFilename, &lc_mask);
+    clock.lap("low-complexity mask");
+  }
   Peng peng(Global::strand, Global::bgModelOrder, Global::maxOptBgModelOrder, Global::inputSequenceSet, bgModel);
 
   PengParameters params;
@@ -110,16 +126,15 @@ int main(int nargs, char** args) {
   if (Global::eraseFilename)
     std::cout << "erase mode: up to " << Global::eraseRounds << " further round" << (Global::eraseRounds == 1 ? "" : "s")
               << " on the input with the found motifs' sites (p-value <= " << Global::erasePvalue << ") masked" << std::endl
-              << "erase round 1: the input as it is" << std::endl;
+              << (lc_mask.attached ? "erase round 1: the input behind the low-complexity mask" : "erase round 1: the input as it is")
+              << std::endl;
   peng.process(params, result);
+  if (lc_mask.attached) pengk_host::override_packed_input(nullptr, nullptr);
   clock.lap("process (count, sweep, hill-climb, PWMs, EM, merging)");
   peng.filter_redundancy(Global::mergeBitfactorThreshold, result);
   std::vector<MotifScore> scores;
-  // (the erasing, the scoring, the sites, the centrality, the refinement, the spacing, the first-order models and the
-  // database enrichment share one scan layout of the input)
-  std::unique_ptr<ScanInput> scan;
-  if (Global::scoreMotifs || Global::sitesFilename || Global::centralityFilename || Global::refineFilename ||
-      Global::spacingFilename || Global::dinucFilename || Global::enrichFilename || Global::eraseFilename) {
+  if (!scan && (Global::scoreMotifs || Global::sitesFilename || Global::centralityFilename || Global::refineFilename ||
+      Global::spacingFilename || Global::dinucFilename || Global::enrichFilename || Global::eraseFilename)) {
     scan.reset(new ScanInput);
     build_scan_input(*Global::inputSequenceSet, scan.get());
   }
@@ -127,9 +142,11 @@ int main(int nargs, char** args) {
   // the unmasked scan input
   if (Global::eraseFilename) {
     run_erase_rounds(peng, params, result, *Global::inputSequenceSet, *scan, *bgModel, Global::strand == Strand::BOTH_STRANDS,
-                     Global::erasePvalue, Global::eraseRounds, Global::mergeBitfactorThreshold, Global::eraseFilename);
+                     Global::erasePvalue, Global::eraseRounds, Global::mergeBitfactorThreshold, Global::eraseFilename,
+                     lc_mask.erase_valid());
     clock.lap("erase rounds");
   }
+  if (lc_mask.control_attached) pengk_host::override_control_input(nullptr, nullptr);
   // (--enrich scores against the negatives of --score-motifs and --dinuc: with it they are built once, for all three)
   // (--score-negatives control: the control set, matched to the input, serves whichever of the three is asked for)
   std::unique_ptr<Negatives> negatives;

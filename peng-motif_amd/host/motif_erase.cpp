@@ -50,7 +50,7 @@ bool redundant(IUPACPattern* kept, IUPACPattern* p, BackgroundModel& bg, float f
 
 void run_erase_rounds(Peng& peng, PengParameters& params, std::vector<IUPACPattern*>& result, SequenceSet& set,
                       const ScanInput& in, BackgroundModel& bg, bool both_strands, double pvalue, int rounds,
-                      float merge_bit_factor_threshold, const std::string& path) {
+                      float merge_bit_factor_threshold, const std::string& path, const uint32_t* initial_valid) {
   using pengk_host::check;
   using pengk_host::DeviceBuffer;
   pengk_host::Lap lap("  erase: ");
@@ -65,9 +65,9 @@ void run_erase_rounds(Peng& peng, PengParameters& params, std::vector<IUPACPatte
   report[0].seeds = peng.last_seeds;
   report[0].windows = peng.last_windows;
   std::vector<IUPACPattern*> prev(result);  // the motifs whose sites are masked next
-  // validity words: the round reads `cur` (round 2: the input's own) and writes `next`
+  // validity words: the round reads `cur` (round 2: the input's own, or what --mask-low-complexity left of them) and writes `next`
   DeviceBuffer<uint32_t> va((size_t)in.n_words), vb((size_t)in.n_words);
-  const uint32_t* cur = in.d_valid.get();
+  const uint32_t* cur = initial_valid ? initial_valid : in.d_valid.get();
   uint32_t* next = va.get();
   DeviceBuffer<uint64_t> d_tot;
   DeviceBuffer<uint64_t> d_words, d_items, d_seq_base(n_local), d_seq_item(n_local);
@@ -112,6 +112,11 @@ void run_erase_rounds(Peng& peng, PengParameters& params, std::vector<IUPACPatte
       dump_file(sub + "/erase_S.i32", S.data(), S.size() * sizeof(int32_t));
       dump_file(sub + "/erase_len.i32", len.data(), len.size() * sizeof(int32_t));
       dump_file(sub + "/erase_thr.i32", thr.data(), thr.size() * sizeof(int32_t));
+      if (initial_valid) {  // (--mask-low-complexity: the validity words that round is searched on)
+        std::vector<uint32_t> v((size_t)in.n_words);
+        check(pengk_memcpy_d2h(ctx, v.data(), next, v.size() * sizeof(uint32_t)), "pengk_memcpy_d2h");
+        dump_file(sub + "/erase_valid.u32", v.data(), v.size() * sizeof(uint32_t));
+      }
     }
     lap("thresholds + mask");
     if (r > rounds || rd.seeds == 0 || erased == 0) break;

@@ -59,6 +59,7 @@ void build_scan_input(SequenceSet& set, ScanInput* in) {
     nt = (unsigned)std::max<size_t>(1, std::min<size_t>(nt, NC));
     std::vector<std::thread> th;
     std::vector<int> rc(nt, PENGK_OK);
+    std::vector<uint64_t> ones(nt, 0);  // the valid bases of each thread's chunks (--mask-low-complexity reports them)
     for (unsigned t = 0; t < nt; ++t)
       th.emplace_back([&, t] {
         for (size_t c = t; c < NC && rc[t] == PENGK_OK; c += nt) {
@@ -66,10 +67,15 @@ void build_scan_input(SequenceSet& set, ScanInput* in) {
           if (ch.n == 0) continue;
           rc[t] = pengk_scan_layout_build(ch.codes, ch.offs.data(), (int64_t)ch.n, word0[c], words.data(), valid.data(),
                                           offs.data() + ch.first, lens.data() + ch.first);
+          uint64_t n1 = 0;
+          for (uint64_t w = word0[c]; w < word0[c + 1]; ++w) n1 += (unsigned)__builtin_popcount(valid[w]);
+          ones[t] += n1;
         }
       });
     for (auto& x : th) x.join();
     for (int r : rc) check(r, "pengk_scan_layout_build");
+    in->valid_bases = 0;
+    for (uint64_t n1 : ones) in->valid_bases += n1;
   }
   lap("built");
   in->n_local = n_local;

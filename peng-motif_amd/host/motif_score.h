@@ -20,6 +20,7 @@
 struct ScanInput {
   size_t n_local = 0;
   uint64_t n_words = 0;
+  uint64_t valid_bases = 0;  // set validity bits of this rank's records (counted while the layout is built)
   pengk_host::DeviceBuffer<uint64_t> d_words;
   pengk_host::DeviceBuffer<uint32_t> d_valid;
   pengk_host::DeviceBuffer<int64_t> d_offs;
