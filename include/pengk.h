@@ -502,6 +502,28 @@ typedef struct {
  * h_pos above n_pos or of h_neg above n_neg is PENGK_ERR_ARG. */
 int pengk_enrich_summary(const uint64_t* h_pos, const uint64_t* h_neg, uint64_t nbins, int32_t thr, uint64_t n_pos,
                          uint64_t n_neg, pengk_enrichment* out);
+typedef struct {
+  int32_t threshold;             /* pengk_enrich_summary's threshold on the two training histograms */
+  uint32_t n_thresholds;         /* T: the thresholds it tried there */
+  uint64_t train_pos_hits;       /* a, b of that call: what the motif was chosen on */
+  uint64_t train_neg_hits;
+  double train_log10_adj_pvalue; /* its log10_adj_pvalue: Bonferroni over T, and still fitted to these sequences */
+  uint64_t hold_pos_hits;        /* a': hold-out input sequences with a best score >= threshold */
+  uint64_t hold_neg_hits;        /* b': hold-out negatives likewise */
+  double hold_log10_pvalue;      /* log10 P(X >= a'), X ~ Hypergeometric(n_hold_pos + n_hold_neg, a' + b', n_hold_pos) */
+  double hold_enrichment;        /* ((a' + 1) / (n_hold_pos + 1)) / ((b' + 1) / (n_hold_neg + 1)) */
+} pengk_holdout;
+/* Pure CPU.  One motif's test on sequences it was not fitted to (--holdout): four histograms of
+ * pengk_motif_enrich with the same thr and nbins (training and hold-out share of the input and of the negatives, summed
+ * over all ranks) and the four scored counts.  The threshold is the one pengk_enrich_summary(h_train_pos, h_train_neg,
+ * nbins, thr, n_train_pos, n_train_neg) reports, with its T, hits and log10_adj_pvalue.  a' / b' = the sums of h_hold_pos /
+ * h_hold_neg over the bins k >= threshold - thr; hold_log10_pvalue = pengk_hypergeom_log10_sf(n_hold_pos + n_hold_neg,
+ * a' + b', n_hold_pos, a'): one threshold, fixed before the hold-out was looked at, so no Bonferroni factor.  T = 0 (no
+ * training sequence in any bin): threshold thr + nbins, no hits, both logs 0, hold_enrichment by the same formula.  A sum
+ * of a histogram above its n is PENGK_ERR_ARG. */
+int pengk_holdout_summary(const uint64_t* h_train_pos, const uint64_t* h_train_neg, const uint64_t* h_hold_pos,
+                          const uint64_t* h_hold_neg, uint64_t nbins, int32_t thr, uint64_t n_train_pos, uint64_t n_train_neg,
+                          uint64_t n_hold_pos, uint64_t n_hold_neg, pengk_holdout* out);
 /* Pure CPU.  Benjamini-Hochberg q-values of one motif's sites from its histogram (h_hist[k]: the sites with score t + k,
  * nbins = hi - t + 1 bins, summed over all ranks), the number of tests n_tests (d_tests, summed likewise) and
  * h_tail_from_thr = tail + (t - lo) of pengk_score_tail_pvalues.  n(k) = sum over k' >= k of h_hist[k'] (uint64, from
@@ -611,6 +633,24 @@ int pengk_match_quotas(const uint64_t* h_in, const uint64_t* h_ctrl, uint64_t ra
 int pengk_select_strata(pengk_ctx* ctx, const uint16_t* d_stratum, uint64_t n_seq, const uint64_t* h_count, const uint64_t* h_quota,
                         const uint64_t* h_rank0, const int64_t* d_offs, const uint32_t* d_lens, int64_t* d_sel_offs,
                         uint32_t* d_sel_lens, uint32_t* d_sel_index, uint64_t* n_sel_out);
+
+/* ---- a hold-out share (--holdout: motifs are found on one share of the input and tested on the rest, as STREME sets 10 %
+ *      of its sequences aside; this project's own definitions) --------------------------------------
+ * Integer throughout: a numpy restatement and any sharding give the same bits.  Sequence i of this call's n_seq has the
+ * global index g = seq0 + (d_index ? d_index[i] : i) and the class 1 (hold-out) iff
+ *   mix64(seed + 0x9E3779B97F4A7C15 * (g + 1)) >> 32 < threshold      (mod 2^64; mix64 = the splitmix64 finalizer),
+ * else 0 (training); threshold in 0 .. 2^32 (0: none held out, 2^32: all), a share of threshold / 2^32.  Both classes'
+ * d_offs[i] / d_lens[i] / i are written compacted, in file order, to d_offs0 / d_lens0 / d_index0 (training) and d_offs1 /
+ * d_lens1 / d_index1 (hold-out), room for n_seq entries each -- with the words of the layout that d_offs / d_lens belong
+ * to, two scan layouts; *n0_out / *n1_out (host) = the two counts.  d_class[i] (n_seq uint8) receives the class when
+ * given.  d_index (NULL, or n_seq local indices such as pengk_select_strata's d_sel_index): a set that was reduced before
+ * is split by its sequences' indices in the file, so a matched and an unmatched control put a sequence on the same side.
+ * n_seq = 0 does nothing.  PENGK_ERR_ARG, and nothing written: seq0 + n_seq > 2^32, threshold > 2^32, an output that
+ * overlaps d_index, d_offs or d_lens.  Synchronises with the host. */
+int pengk_split_sequences(pengk_ctx* ctx, uint64_t seed, uint64_t seq0, uint64_t n_seq, uint64_t threshold, const uint32_t* d_index,
+                          const int64_t* d_offs, const uint32_t* d_lens, uint8_t* d_class, int64_t* d_offs0, uint32_t* d_lens0,
+                          uint32_t* d_index0, uint64_t* n0_out, int64_t* d_offs1, uint32_t* d_lens1, uint32_t* d_index1,
+                          uint64_t* n1_out);
 
 /* ---- central enrichment (--centrality: which found motifs sit at the centres of the input sequences; CentriMo's
  *      site distribution and binomial test) ------------------------------------------------------------

@@ -37,7 +37,7 @@ EXPORTS = [
     "pengk_score_tail_pvalues", "pengk_score_threshold", "pengk_sites_count", "pengk_sites_slices", "pengk_sites_emit",
     "pengk_sites_histograms", "pengk_sites_qvalues", "pengk_qvalue_threshold",
     "pengk_mask_sites", "pengk_pack_scan_sizes", "pengk_pack_scan", "pengk_mask_low_complexity",
-    "pengk_seq_strata", "pengk_match_quotas", "pengk_select_strata",
+    "pengk_seq_strata", "pengk_match_quotas", "pengk_select_strata", "pengk_split_sequences", "pengk_holdout_summary",
     "pengk_motif_enrich", "pengk_hypergeom_log10_sf", "pengk_enrich_summary",
     "pengk_motif_best_sites", "pengk_centrality_histograms", "pengk_centrality_summary", "pengk_binomial_log10_sf",
     "pengk_site_profiles", "pengk_profile_refine",
@@ -64,6 +64,12 @@ class CentralityStruct(C.Structure):
 class EnrichmentStruct(C.Structure):
     _fields_ = [("threshold", C.c_int32), ("n_thresholds", C.c_uint32), ("pos_hits", C.c_uint64), ("neg_hits", C.c_uint64),
                 ("enrichment", C.c_double), ("log10_pvalue", C.c_double), ("log10_adj_pvalue", C.c_double)]
+
+
+class HoldoutStruct(C.Structure):
+    _fields_ = [("threshold", C.c_int32), ("n_thresholds", C.c_uint32), ("train_pos_hits", C.c_uint64),
+                ("train_neg_hits", C.c_uint64), ("train_log10_adj_pvalue", C.c_double), ("hold_pos_hits", C.c_uint64),
+                ("hold_neg_hits", C.c_uint64), ("hold_log10_pvalue", C.c_double), ("hold_enrichment", C.c_double)]
 
 
 class SpacingStruct(C.Structure):
@@ -181,6 +187,9 @@ def lib():
         L.pengk_motif_enrich.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp]
         L.pengk_hypergeom_log10_sf.argtypes = [u64, u64, u64, u64, C.POINTER(C.c_double)]
         L.pengk_enrich_summary.argtypes = [vp, vp, u64, C.c_int32, u64, u64, C.POINTER(EnrichmentStruct)]
+        L.pengk_split_sequences.argtypes = [vp, u64, u64, u64, u64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(u64), vp, vp, vp,
+                                            C.POINTER(u64)]
+        L.pengk_holdout_summary.argtypes = [vp, vp, vp, vp, u64, C.c_int32, u64, u64, u64, u64, C.POINTER(HoldoutStruct)]
         L.pengk_qvalue_threshold.argtypes = [vp, u64, C.c_int32, C.c_double, C.POINTER(C.c_int32)]
         L.pengk_sites_slices.argtypes = [vp, vp, u64, C.c_int, vp, u64, vp, vp, C.POINTER(u64)]
         L.pengk_sites_emit.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, vp, vp, C.c_int, vp, vp, u64, u64, vp, u64]
@@ -349,6 +358,17 @@ def enrich_summary(pos_hist, neg_hist, thr, n_pos, n_neg):
     _check(lib().pengk_enrich_summary(p.ctypes.data if len(p) else None, n.ctypes.data if len(n) else None, len(p), int(thr),
                                       int(n_pos), int(n_neg), C.byref(out)))
     return {k: getattr(out, k) for k, _ in EnrichmentStruct._fields_}
+
+
+def holdout_summary(train_pos, train_neg, hold_pos, hold_neg, thr, n_train_pos, n_train_neg, n_hold_pos, n_hold_neg):
+    """one found motif's test on the hold-out share from its four histograms of Context.motif_enrich (bin k = score thr + k)
+    and the scored sequences of the four sets (pengk_holdout_summary, CPU): a dict with the fields of pengk_holdout"""
+    h = [np.ascontiguousarray(x, np.uint64) for x in (train_pos, train_neg, hold_pos, hold_neg)]
+    assert h[0].shape == h[1].shape == h[2].shape == h[3].shape
+    out = HoldoutStruct()
+    _check(lib().pengk_holdout_summary(*[x.ctypes.data if len(x) else None for x in h], len(h[0]), int(thr), int(n_train_pos),
+                                       int(n_train_neg), int(n_hold_pos), int(n_hold_neg), C.byref(out)))
+    return {k: getattr(out, k) for k, _ in HoldoutStruct._fields_}
 
 
 def spacing_summary(hist_gaps, hist_lengths, max_gap, max_len, w_a, w_b, n_classes, n, n_a, n_b, n_pairs):
@@ -822,6 +842,22 @@ class Context:
         _check(lib().pengk_select_strata(self.h, _ptr(stratum), n_seq, c.ctypes.data, q.ctypes.data, r0.ctypes.data, _ptr(offs),
                                          _ptr(lens), _ptr(so), _ptr(sl), _ptr(si), C.byref(n_sel)))
         return so, sl, si, int(n_sel.value)
+
+    # ---- a hold-out share (--holdout) ------------------------------------------------------------------------
+    def split_sequences(self, seed, seq0, n_seq, threshold, offs, lens, index=None, want_class=False):
+        """((offs0, lens0, index0, n0), (offs1, lens1, index1, n1), cls): the training and the hold-out share of this call's
+        n_seq sequences as compacted device arrays -- with the words of the layout that offs / lens belong to, two scan
+        layouts -- and, want_class, the class of every sequence as a device uint8 array, else None
+        (pengk_split_sequences).  index: a device uint32 array of local indices to hash instead of 0 .. n_seq - 1."""
+        m = max(n_seq, 1)
+        out = [(self.empty(m, np.int64), self.empty(m, np.uint32), self.empty(m, np.uint32)) for _ in range(2)]
+        cls = self.empty(m, np.uint8) if want_class else None
+        n0, n1 = C.c_uint64(), C.c_uint64()
+        _check(lib().pengk_split_sequences(self.h, int(seed), int(seq0), int(n_seq), int(threshold),
+                                           None if index is None else _ptr(index), _ptr(offs), _ptr(lens),
+                                           None if cls is None else _ptr(cls), _ptr(out[0][0]), _ptr(out[0][1]), _ptr(out[0][2]),
+                                           C.byref(n0), _ptr(out[1][0]), _ptr(out[1][1]), _ptr(out[1][2]), C.byref(n1)))
+        return out[0] + (int(n0.value),), out[1] + (int(n1.value),), cls
 
     def sites_histograms(self, scan, S, lens, both, thr, hi, counts=None, hist=None, tests=None, offs=None):
         """(hists, tests): hists[m] (uint64, max(0, hi[m] - thr[m] + 1) bins) the sites of motif m by score - thr[m], tests[m]

@@ -82,6 +82,11 @@ double Global::erasePvalue = 1e-4;
 bool Global::maskLowComplexity = false;
 int Global::maskThreshold = 20;
 char* Global::maskReportFilename = nullptr;
+char* Global::holdoutFilename = nullptr;
+double Global::holdoutFraction = 0.1;
+unsigned long long Global::holdoutThreshold = 0;
+unsigned long long Global::holdoutSeed = 1;   // (--score-seed's default)
+double Global::holdoutPvalue = 1e-3;          // (--enrich-pvalue's default)
 bool Global::discriminative = false;
 double Global::discriminativePseudocount = 1.0;
 bool Global::scoreNegativesControl = false;
@@ -105,7 +110,7 @@ void Global::init(int nargs, char* args[]) {
   // (the scoring, the sites, the centrality, the refinement, the spacing, the first-order models and the database
   // enrichment scan the input after the motifs are found)
   pengk_host::keep_host_codes(scoreMotifs || sitesFilename || centralityFilename || refineFilename || spacingFilename ||
-                              dinucFilename || enrichFilename || eraseFilename || maskLowComplexity);
+                              dinucFilename || enrichFilename || eraseFilename || maskLowComplexity || holdoutFilename);
   // both strands are handled inside the count; sequences are always read single stranded
   // ... and every chunk of the input set is packed and sent to the device while the rest is still being read
   pengk_host::begin_streaming_pack(patternLength);
@@ -192,6 +197,7 @@ void Global::readArguments(int nargs, char* args[]) {
     exit(-1);
   }
   inputSequenceFilename = args[1];
+  const char* holdout_option = nullptr;  // the last option given that only means something with --holdout
   const char* mask_option = nullptr;  // the last option given that only means something with --mask-low-complexity
   for (int i = 2; i < nargs; i++) {
     const char* a = args[i];
@@ -483,6 +489,39 @@ void Global::readArguments(int nargs, char* args[]) {
     } else if (!strcmp(a, "--mask-report")) {
       maskReportFilename = (char*)need(i, nargs, args, printHelp);
       mask_option = "--mask-report";
+    } else if (!strcmp(a, "--holdout")) {
+      holdoutFilename = (char*)need(i, nargs, args, printHelp);
+    } else if (!strcmp(a, "--holdout-fraction")) {
+      const char* v = need(i, nargs, args, printHelp);
+      char* end = nullptr;
+      holdoutFraction = std::strtod(v, &end);
+      // (the threshold of the split: a fraction that rounds to no sequence at all is refused with the rest)
+      if (end == v || *end || !(holdoutFraction > 0.0 && holdoutFraction <= 0.5) || (uint64_t)(holdoutFraction * 4294967296.0) == 0) {
+        printHelp();
+        log_line("ERROR", "--holdout-fraction must be a number in (0, 0.5], 2^-32 at the least");
+        exit(4);
+      }
+      holdout_option = "--holdout-fraction";
+    } else if (!strcmp(a, "--holdout-seed")) {
+      const char* v = need(i, nargs, args, printHelp);
+      char* end = nullptr;
+      holdoutSeed = std::strtoull(v, &end, 10);
+      if (end == v || *end || *v == '-') {
+        printHelp();
+        log_line("ERROR", "--holdout-seed must be an integer, 0 or above");
+        exit(4);
+      }
+      holdout_option = "--holdout-seed";
+    } else if (!strcmp(a, "--holdout-pvalue")) {
+      const char* v = need(i, nargs, args, printHelp);
+      char* end = nullptr;
+      holdoutPvalue = std::strtod(v, &end);
+      if (end == v || *end || !(holdoutPvalue > 0.0 && holdoutPvalue <= 1.0)) {
+        printHelp();
+        log_line("ERROR", "--holdout-pvalue must be a number in (0, 1]");
+        exit(4);
+      }
+      holdout_option = "--holdout-pvalue";
     } else if (!strcmp(a, "--discriminative")) {
       discriminative = true;
     } else if (!strcmp(a, "--discriminative-pseudocount")) {
@@ -537,6 +576,12 @@ void Global::readArguments(int nargs, char* args[]) {
       if (pengk_host::rank() == 0) log_line("WARNING", std::string("Ignoring unknown option ") + a);
     }
   }
+  if (holdout_option && !holdoutFilename) {
+    printHelp();
+    log_line("ERROR", std::string(holdout_option) + " requires --holdout");
+    exit(4);
+  }
+  holdoutThreshold = (unsigned long long)(holdoutFraction * 4294967296.0);
   if (mask_option && !maskLowComplexity) {
     printHelp();
     log_line("ERROR", std::string(mask_option) + " requires --mask-low-complexity");
@@ -587,6 +632,14 @@ void Global::printHelp() {
   printf("                                 the rounds of --erase start from the masked input; the reports scan the input as it is\n");
   printf("  --mask-threshold INT           score threshold of --mask-low-complexity, 1..1000 (default 20, DUST's)\n");
   printf("  --mask-report FILE             the masked runs: sequence index, start, end (half-open), tab-separated\n");
+  printf("  --holdout FILE                 set a share of the input aside before anything is counted, find the motifs on the\n");
+  printf("                                 rest and test each on the share it never saw.  FILE: one line per motif with its\n");
+  printf("                                 hits on both shares and the hold-out p-value, the unbiased one.  Negatives as\n");
+  printf("                                 --score-negatives says; with --discriminative the control set is split likewise;\n");
+  printf("                                 every other report scans the whole input\n");
+  printf("  --holdout-fraction FLOAT       the share set aside, in (0, 0.5] (default 0.1)\n");
+  printf("  --holdout-seed INT             seed of the split (default 1)\n");
+  printf("  --holdout-pvalue FLOAT         per-window p-value of the lowest score threshold tried, in (0, 1] (default 1e-3)\n");
   printf("  --erase FILE                   after the search, mask the sites of the motifs found and search what is left\n");
   printf("                                 again; the later rounds' motifs are appended.  FILE: one line per round and motif\n");
   printf("  --erase-rounds INT             further rounds of --erase, 1..8 (default 1); a round that finds or erases\n");

@@ -98,6 +98,11 @@ class Global {
   static bool maskLowComplexity;             // --mask-low-complexity (new: symmetric-DUST masking in front of round 1)
   static int maskThreshold;                  // --mask-threshold: 1..1000 (DUST's 20)
   static char* maskReportFilename;           // --mask-report: the masked runs, BED-like
+  static char* holdoutFilename;              // --holdout (new: motifs are found on one share of the input and tested on the rest)
+  static double holdoutFraction;             // --holdout-fraction: the share set aside, in (0, 0.5]
+  static unsigned long long holdoutThreshold; // ... as the split's threshold: (uint64_t)(fraction * 2^32)
+  static unsigned long long holdoutSeed;     // --holdout-seed
+  static double holdoutPvalue;               // --holdout-pvalue: the floor of the score thresholds tried
   static bool discriminative;                // --discriminative (new: the k-mer sweep held to the control set's counts)
   static double discriminativePseudocount;   // --discriminative-pseudocount
   static bool scoreNegativesControl;         // --score-negatives control (new: the --background-sequences file as negatives, matched to the input)

@@ -28,7 +28,7 @@ BasePattern::BasePattern(const size_t pattern_length, Strand s, const int k, con
   background_model = bg;
   init(pattern_length);
   number_patterns = factor[pattern_length];
-  n_sequences = sequence_set->getN();
+  n_sequences = pengk_host::sequence_count(sequence_set);
   this->k = k;
   this->max_k = std::max(k, max_k);
   const int W = (int)pattern_length;

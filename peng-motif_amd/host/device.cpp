@@ -371,6 +371,13 @@ void override_control_input(SequenceSet* set, const PackedInput* in) {
   g_control_set = in ? set : nullptr;
   g_control = in;
 }
+static SequenceSet* g_count_set = nullptr;
+static size_t g_count = 0;
+void override_sequence_count(SequenceSet* set, size_t n) {
+  g_count_set = set;
+  g_count = n;
+}
+size_t sequence_count(SequenceSet* set) { return g_count_set && g_count_set == set ? g_count : set->getN(); }
 void set_dump_subdir(const std::string& sub) { g_dump_subdir = sub; }
 const std::string& dump_subdir() { return g_dump_subdir; }
 

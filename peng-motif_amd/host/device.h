@@ -58,6 +58,10 @@ void override_packed_input(::SequenceSet* set, const PackedInput* in);
 // --mask-low-complexity with --discriminative: a second slot, for the control set (its masked copy, packed on the
 // device), which the rounds of --erase leave alone; nullptr ends that.  Empty without the flag.
 void override_control_input(::SequenceSet* set, const PackedInput* in);
+// --holdout: from now on sequence_count(set) is n (the training sequences of the set, over all ranks) instead of
+// set->getN(): the search sees the training share as its whole input; set = nullptr ends that
+void override_sequence_count(::SequenceSet* set, size_t n);
+size_t sequence_count(::SequenceSet* set);
 // PENGK_DUMP_TABLES: the folder below the one it names that BasePattern writes into ("" = that folder itself)
 void set_dump_subdir(const std::string& sub);
 const std::string& dump_subdir();

@@ -20,6 +20,7 @@
 #include "motif_dust.h"
 #include "motif_enrich.h"
 #include "motif_erase.h"
+#include "motif_holdout.h"
 #include "motif_match.h"
 #include "motif_refine.h"
 #include "motif_spacing.h"
@@ -101,6 +102,27 @@ int main(int nargs, char** args) {
                         Global::patternLength, Global::maskThreshold, Global::maskReportFilename, &lc_mask);
     clock.lap("low-complexity mask");
   }
+  // --holdout: a share of the input (and with --discriminative of the control set) is set aside before anything is
+  // counted; round 1 and the rounds of --erase see the training share, behind the mask if there is one; the background
+  // model above and every other report below see the whole input
+  Holdout holdout;
+  HoldoutSettings holdout_settings;
+  if (Global::holdoutFilename && Global::patternLength >= PENGK_MIN_W && Global::patternLength <= PENGK_MAX_W) {
+    holdout_settings.fraction = Global::holdoutFraction;
+    holdout_settings.threshold = Global::holdoutThreshold;
+    holdout_settings.seed = Global::holdoutSeed;
+    holdout_settings.pvalue = Global::holdoutPvalue;
+    if (!scan) {
+      scan.reset(new ScanInput);
+      build_scan_input(*Global::inputSequenceSet, scan.get());
+    }
+    split_holdout(*Global::inputSequenceSet, *scan, lc_mask.attached ? lc_mask.input.d_valid.get() : nullptr,
+                  Global::discriminative ? Global::backgroundSequenceSet : nullptr,
+                  lc_mask.control_attached ? lc_mask.control.d_valid.get() : nullptr, Global::patternLength, holdout_settings,
+                  &holdout);
+    clock.lap("holdout split");
+  }
+  const ScanSubset training = holdout.input.share(0);
   Peng peng(Global::strand, Global::bgModelOrder, Global::maxOptBgModelOrder, Global::inputSequenceSet, bgModel);
 
   PengParameters params;
@@ -129,7 +151,7 @@ int main(int nargs, char** args) {
               << (lc_mask.attached ? "erase round 1: the input behind the low-complexity mask" : "erase round 1: the input as it is")
               << std::endl;
   peng.process(params, result);
-  if (lc_mask.attached) pengk_host::override_packed_input(nullptr, nullptr);
+  if (lc_mask.attached || holdout.attached) pengk_host::override_packed_input(nullptr, nullptr);
   clock.lap("process (count, sweep, hill-climb, PWMs, EM, merging)");
   peng.filter_redundancy(Global::mergeBitfactorThreshold, result);
   std::vector<MotifScore> scores;
@@ -143,14 +165,15 @@ int main(int nargs, char** args) {
   if (Global::eraseFilename) {
     run_erase_rounds(peng, params, result, *Global::inputSequenceSet, *scan, *bgModel, Global::strand == Strand::BOTH_STRANDS,
                      Global::erasePvalue, Global::eraseRounds, Global::mergeBitfactorThreshold, Global::eraseFilename,
-                     lc_mask.erase_valid());
+                     lc_mask.erase_valid(), holdout.attached ? &training : nullptr);
     clock.lap("erase rounds");
   }
-  if (lc_mask.control_attached) pengk_host::override_control_input(nullptr, nullptr);
+  if (lc_mask.control_attached || holdout.control_attached) pengk_host::override_control_input(nullptr, nullptr);
+  if (holdout.attached) pengk_host::override_sequence_count(nullptr, 0);
   // (--enrich scores against the negatives of --score-motifs and --dinuc: with it they are built once, for all three)
   // (--score-negatives control: the control set, matched to the input, serves whichever of the three is asked for)
   std::unique_ptr<Negatives> negatives;
-  if (Global::scoreNegativesControl && (Global::scoreMotifs || Global::dinucFilename || Global::enrichFilename)) {
+  if (Global::scoreNegativesControl && (Global::scoreMotifs || Global::dinucFilename || Global::enrichFilename || holdout.attached)) {
     negatives.reset(new Negatives);
     MatchSettings ms;
     ms.gc = Global::controlMatchGc;
@@ -160,7 +183,7 @@ int main(int nargs, char** args) {
     if (Global::controlMatchReportFilename) ms.report_path = Global::controlMatchReportFilename;
     build_control_negatives(*Global::backgroundSequenceSet, *scan, ms, negatives.get());
     clock.lap("control negatives");
-  } else if (Global::enrichFilename) {
+  } else if (Global::enrichFilename || holdout.attached) {
     negatives.reset(new Negatives);
     build_negatives(*Global::inputSequenceSet, *scan, *bgModel, Global::bgModelOrder, Global::scoreSeed,
                     Global::scoreNegativesShuffled, negatives.get());
@@ -188,8 +211,13 @@ int main(int nargs, char** args) {
   // the MEME file's order: as it is, or as the writers sort it (the same sort of the same vector: the same order)
   std::vector<IUPACPattern*> meme_order(result);
   if (!sc && (Global::sitesFilename || Global::centralityFilename || Global::refineFilename || Global::spacingFilename ||
-              Global::dinucFilename))
+              Global::dinucFilename || holdout.attached))
     std::sort(meme_order.begin(), meme_order.end(), sort_IUPAC_patterns);
+  if (holdout.attached) {
+    write_motif_holdout(meme_order, *scan, holdout, *negatives, Global::backgroundSequenceSet, *bgModel,
+                        Global::strand == Strand::BOTH_STRANDS, holdout_settings, Global::holdoutFilename);
+    clock.lap("holdout");
+  }
   if (Global::sitesFilename) {
     write_motif_sites(meme_order, *Global::inputSequenceSet, *scan, *bgModel, Global::strand == Strand::BOTH_STRANDS,
                       Global::sitesPvalue, Global::sitesQvalue, Global::sitesQvalueMax, Global::sitesFilename);

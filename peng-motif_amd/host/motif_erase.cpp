@@ -50,14 +50,17 @@ bool redundant(IUPACPattern* kept, IUPACPattern* p, BackgroundModel& bg, float f
 
 void run_erase_rounds(Peng& peng, PengParameters& params, std::vector<IUPACPattern*>& result, SequenceSet& set,
                       const ScanInput& in, BackgroundModel& bg, bool both_strands, double pvalue, int rounds,
-                      float merge_bit_factor_threshold, const std::string& path, const uint32_t* initial_valid) {
+                      float merge_bit_factor_threshold, const std::string& path, const uint32_t* initial_valid,
+                      const ScanSubset* subset) {
   using pengk_host::check;
   using pengk_host::DeviceBuffer;
   pengk_host::Lap lap("  erase: ");
   pengk_ctx* ctx = pengk_host::context();
   const int W = (int)params.max_pattern_length;
   const int both = both_strands ? 1 : 0;
-  const size_t n_local = in.n_local;
+  const size_t n_local = subset ? subset->n : in.n_local;
+  const int64_t* d_offs = subset ? subset->d_offs : in.d_offs.get();
+  const uint32_t* d_lens = subset ? subset->d_lens : in.d_lens.get();
   const float* bg0 = bg.getV()[0];
   const char* dump_dir = pengk_host::rank() == 0 ? std::getenv("PENGK_DUMP_TABLES") : nullptr;
 
@@ -68,6 +71,10 @@ void run_erase_rounds(Peng& peng, PengParameters& params, std::vector<IUPACPatte
   // validity words: the round reads `cur` (round 2: the input's own, or what --mask-low-complexity left of them) and writes `next`
   DeviceBuffer<uint32_t> va((size_t)in.n_words), vb((size_t)in.n_words);
   const uint32_t* cur = initial_valid ? initial_valid : in.d_valid.get();
+  if (subset) {  // (the words of the sequences outside the subset are never written: zero, not whatever the buffer held)
+    check(pengk_memset(ctx, va.get(), 0, (size_t)in.n_words * sizeof(uint32_t)), "pengk_memset");
+    check(pengk_memset(ctx, vb.get(), 0, (size_t)in.n_words * sizeof(uint32_t)), "pengk_memset");
+  }
   uint32_t* next = va.get();
   DeviceBuffer<uint64_t> d_tot;
   DeviceBuffer<uint64_t> d_words, d_items, d_seq_base(n_local), d_seq_item(n_local);
@@ -91,7 +98,7 @@ void run_erase_rounds(Peng& peng, PengParameters& params, std::vector<IUPACPatte
     // the mask of these motifs over what this round searched; site and erased counts summed over the ranks
     d_tot.resize((size_t)n_motifs + 1);
     check(pengk_memset(ctx, d_tot.get(), 0, ((size_t)n_motifs + 1) * sizeof(uint64_t)), "pengk_memset");
-    check(pengk_mask_sites(ctx, in.d_words.get(), cur, in.d_offs.get(), in.d_lens.get(), n_local, n_motifs, S.data(), len.data(),
+    check(pengk_mask_sites(ctx, in.d_words.get(), cur, d_offs, d_lens, n_local, n_motifs, S.data(), len.data(),
                            both, thr.data(), next, d_tot.get(), d_tot.get() + n_motifs),
           "pengk_mask_sites");
     std::vector<long long> tot((size_t)n_motifs + 1, 0);
@@ -124,11 +131,11 @@ void run_erase_rounds(Peng& peng, PengParameters& params, std::vector<IUPACPatte
 
     // the masked set in the count layout, attached in place of the input's
     pengk_packed pk;
-    check(pengk_pack_scan_sizes(ctx, next, in.d_offs.get(), in.d_lens.get(), n_local, W, 0, d_seq_base.get(), d_seq_item.get(), &pk),
+    check(pengk_pack_scan_sizes(ctx, next, d_offs, d_lens, n_local, W, 0, d_seq_base.get(), d_seq_item.get(), &pk),
           "pengk_pack_scan_sizes");
     d_words.resize(pk.n_words);
     d_items.resize(pk.n_items + 1);
-    check(pengk_pack_scan(ctx, in.d_words.get(), next, in.d_offs.get(), in.d_lens.get(), n_local, W, 0, d_seq_base.get(),
+    check(pengk_pack_scan(ctx, in.d_words.get(), next, d_offs, d_lens, n_local, W, 0, d_seq_base.get(),
                           d_seq_item.get(), d_words.get(), pk.n_words, d_items.get(), pk.n_items),
           "pengk_pack_scan");
     masked.W = W;

@@ -18,9 +18,12 @@
 // when the previous one reported no motif or erased no base.  `path`: the report, one line per round and motif (rank 0).
 // initial_valid: the validity words round 1 was searched on when they are not the input's own (--mask-low-complexity: what
 // that mask took stays out of every round).
+// subset (--holdout): the sequences of `in` that are masked, packed and searched -- the training share -- in place of all of
+// them; the validity words of the others stay zero.
 // Collective in a multi-rank run: every rank masks and packs its own records, the counts are summed as in round 1.
 void run_erase_rounds(Peng& peng, PengParameters& params, std::vector<IUPACPattern*>& result, SequenceSet& set,
                       const ScanInput& in, BackgroundModel& bg, bool both_strands, double pvalue, int rounds,
-                      float merge_bit_factor_threshold, const std::string& path, const uint32_t* initial_valid = nullptr);
+                      float merge_bit_factor_threshold, const std::string& path, const uint32_t* initial_valid = nullptr,
+                      const ScanSubset* subset = nullptr);
 
 #endif

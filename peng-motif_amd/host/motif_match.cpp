@@ -103,7 +103,8 @@ void build_control_negatives(SequenceSet& control, const ScanInput& in, const Ma
 
   out->d_sel_offs.resize(std::max<size_t>(n_ctrl, 1));
   out->d_sel_lens.resize(std::max<size_t>(n_ctrl, 1));
-  DeviceBuffer<uint32_t> d_index(std::max<size_t>(n_ctrl, 1));
+  out->d_sel_index.resize(std::max<size_t>(n_ctrl, 1));
+  const DeviceBuffer<uint32_t>& d_index = out->d_sel_index;
   uint64_t n_sel = 0;
   check(pengk_select_strata(ctx, d_stratum.get(), n_ctrl, h_ctrl, quota.data(), rank0.data(), ctl.d_offs.get(), ctl.d_lens.get(),
                             out->d_sel_offs.get(), out->d_sel_lens.get(), d_index.get(), &n_sel),

@@ -27,6 +27,13 @@ struct ScanInput {
   pengk_host::DeviceBuffer<uint32_t> d_lens;
 };
 void build_scan_input(SequenceSet& set, ScanInput* in);
+// A subset of a scan layout: a shorter pair of offs / lens arrays into the same words (include/pengk.h), which every
+// scan entry accepts as it stands.  What the rounds of --erase take in place of the input's own arrays under --holdout.
+struct ScanSubset {
+  const int64_t* d_offs = nullptr;
+  const uint32_t* d_lens = nullptr;
+  size_t n = 0;
+};
 
 // one entry of the integer log-odds: clamp(lround(100 log2(p / b)), -2000, 2000)
 int32_t log_odds(float p, float b);
@@ -50,6 +57,7 @@ struct Negatives {
   bool selected = false;                          // d_sel_offs / d_sel_lens / n_sel hold the kept ones
   pengk_host::DeviceBuffer<int64_t> d_sel_offs;
   pengk_host::DeviceBuffer<uint32_t> d_sel_lens;
+  pengk_host::DeviceBuffer<uint32_t> d_sel_index;  // ... and their places among this rank's control records (--holdout splits by them)
   size_t n_sel = 0;
   const uint64_t* words() const { return control ? control->d_words.get() : d_words.get(); }
   const uint32_t* valid_or_null() const { return control ? control->d_valid.get() : shuffled ? d_valid.get() : nullptr; }

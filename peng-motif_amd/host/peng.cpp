@@ -47,7 +47,7 @@ Peng::Peng(Strand s, const int k, const int max_opt_k, SequenceSet* sequence_set
   this->k = k;
   max_k = std::max(k, max_opt_k);
   strand = s;
-  n_sequences = sequence_set->getN();
+  n_sequences = pengk_host::sequence_count(sequence_set);
   IUPACAlphabet::init(Alphabet::getAlphabet());
   IUPACPattern::init(max_iupac_pattern_length, bg->getV()[0]);
   bg_model = bg;
@@ -393,7 +393,7 @@ void Peng::optimize_iupac_patterns(OPTIMIZATION_SCORE score_type, BasePattern* b
                                    float enrich_pseudocount_factor) {
   std::set<size_t> seen, best;
   const size_t W = base_patterns->getPatternLength();
-  const size_t pseudo_expected = (size_t)(sequence_set->getN() * enrich_pseudocount_factor);
+  const size_t pseudo_expected = (size_t)(pengk_host::sequence_count(sequence_set) * enrich_pseudocount_factor);
 
   struct Round {
     std::vector<std::pair<IUPACPattern*, float>> accepted;  // every improvement of the round, in the order it was found
