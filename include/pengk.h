@@ -695,6 +695,56 @@ int pengk_centrality_summary(const uint64_t* h_hist_offsets, const uint64_t* h_h
 /* Pure CPU.  log10 P(X >= k), X ~ Binomial(n, p), k <= n, 0 <= p <= 1: the tail pengk_centrality_summary uses. */
 int pengk_binomial_log10_sf(uint64_t n, uint64_t k, double p, double* out);
 
+/* ---- spaced dyads (--dyads: pairs of trinucleotides a fixed number of unconstrained bases apart, the bipartite sites of
+ *      dimeric factors -- CGG n11 CCG, TGG n7 CCA -- that no contiguous word of the k-mer table holds; the question RSAT's
+ *      dyad-analysis answers) ---------------------------------------------------------------------------
+ * This project's own definitions, integer up to the summary: a numpy restatement and any sharding give the same tables.
+ * The numbers are NOT promised to be RSAT's.  Per sequence of the scan layout above, letters s[0..L) and validity bits v
+ * (d_valid = NULL: every base valid), r[p] = the number of consecutive valid bases from p on:
+ *   triplet     one stands at p iff r[p] >= 3; its value t[p] = 16 s[p] + 4 s[p+1] + s[p+2]; it adds 1 to d_mono[t[p]]
+ *   occurrence  for every p and every g in 0 .. max_gap with r[p] >= 6 + g: one occurrence of the dyad (a, g, b), a = t[p],
+ *               b = t[p + 3 + g], key = 64 a + b.  The whole span is valid, spacer included: a masked stretch cuts dyads
+ *               as it cuts words
+ *   strands     with both_strands, key = min(key, 64 rc(b) + rc(a)), rc the reverse complement of a triplet: a dyad that
+ *               is its own reverse complement counts once per position, and an entry that is not canonical is never
+ *               written.  d_mono holds the + strand's triplets either way
+ *   count       d_counts[g * 4096 + key] += 1
+ * d_counts ((max_gap + 1) x 4096 uint64) and d_mono (64 uint64) are ADDED to (caller-zeroed): shards and several calls sum
+ * exactly.  n_seq = 0 does nothing.  PENGK_ERR_ARG: max_gap outside 0 .. PENGK_DYAD_MAX_GAP, both_strands other than 0 / 1,
+ * n_seq >= 2^32.  Asynchronous on the context's stream. */
+#define PENGK_DYAD_MAX_GAP 26 /* a dyad spans at most 32 bases */
+int pengk_dyad_count(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_valid, const int64_t* d_offs,
+                     const uint32_t* d_lens, uint64_t n_seq, int max_gap, int both_strands,
+                     uint64_t* d_counts /* (max_gap + 1) x 4096, ADDED to */, uint64_t* d_mono /* 64, ADDED to */);
+typedef struct {
+  uint32_t gap;           /* g */
+  uint32_t key;           /* 64 a + b (the canonical one on both strands) */
+  uint64_t count;         /* d_counts[g * 4096 + key] */
+  uint64_t positions;     /* T[g]: the sum of row g */
+  double p;               /* the probability under test */
+  double expected;        /* (double)T[g] * p */
+  double log10_pvalue;    /* log10 P(X >= count), X ~ Binomial(T[g], p) */
+  double log10_evalue;    /* log10_pvalue + log10(tests) */
+  double other_gaps_mean; /* the mean count of the same key over the other gaps (0 when max_gap = 0) */
+  uint32_t family;        /* the 1-based rank of the family's head */
+  uint32_t is_head;       /* 1 for the head itself */
+} pengk_dyad;
+/* Pure CPU.  The report from the two tables of pengk_dyad_count (summed over all ranks), in this order.  M = the sum of
+ * h_mono; f(x) = (double)mono[x] / (double)M on one strand, (double)(mono[x] + mono[rc x]) / (2.0 * (double)M) on both;
+ * T[g] = the integer sum of row g; per (g, key): p = f(a) * f(b), on both strands multiplied by 2.0 after that where key
+ * is not its own reverse complement; tests = (max_gap + 1) * (both_strands ? 2080 : 4096).  A dyad is a candidate iff
+ * count >= min_count and (double)count > (double)T[g] * p; log10_pvalue = pengk_binomial_log10_sf(T[g], count, p),
+ * log10_evalue = log10_pvalue + log10((double)tests); candidates with log10_evalue <= log10(max_evalue) are reported,
+ * ordered by (log10_evalue, g, key) ascending.
+ * Families: a dyad is the string over ACGTn of length 6 + g -- a, g times n, b.  Y is related to X iff for some offset o
+ * in -2 .. 2, Y laid at o on X has no column where both hold letters that differ and at least 4 columns where both hold
+ * the same letter; on both strands Y's reverse complement is tried as well.  Walking the report in order, a dyad joins
+ * the first earlier family head it is related to, else it heads a new family.
+ * Only the first `capacity` lines are written to `out`; *n_out is always the full count, so a caller with too small an
+ * array calls again.  M = 0 reports nothing.  PENGK_ERR_ARG: max_gap or both_strands as above, max_evalue not > 0. */
+int pengk_dyad_summary(const uint64_t* h_counts, const uint64_t* h_mono, int max_gap, int both_strands, uint64_t min_count,
+                       double max_evalue, pengk_dyad* out, uint64_t capacity, uint64_t* n_out);
+
 /* ---- motif refinement (--refine: the found motifs re-estimated and extended from their sites, as MEME, HOMER and STREME
  *      end) -------------------------------------------------------------------------------------------
  * Over the scan layout and the best sites of pengk_motif_best_sites.  Integer up to the counts: any slicing, any rank

@@ -40,6 +40,7 @@ EXPORTS = [
     "pengk_seq_strata", "pengk_match_quotas", "pengk_select_strata", "pengk_split_sequences", "pengk_holdout_summary",
     "pengk_motif_enrich", "pengk_hypergeom_log10_sf", "pengk_enrich_summary",
     "pengk_motif_best_sites", "pengk_centrality_histograms", "pengk_centrality_summary", "pengk_binomial_log10_sf",
+    "pengk_dyad_count", "pengk_dyad_summary",
     "pengk_site_profiles", "pengk_profile_refine",
     "pengk_site_pair_profiles", "pengk_dinuc_model", "pengk_motif_scan_dinuc",
     "pengk_spacing_histograms", "pengk_spacing_summary",
@@ -50,6 +51,7 @@ SCORE_SENTINEL = -2 ** 31
 SITES_BLOCK = 4096
 SITE = np.dtype([("seq", np.uint32), ("pos", np.uint32), ("score", np.int32), ("motif_strand", np.uint32)])
 CENTRALITY_MAX_LEN = 65536
+DYAD_MAX_GAP = 26
 SPACING_MAX_MOTIFS = 64
 SPACING_MAX_GAP = 1024
 COMPARE_BINS = 257
@@ -59,6 +61,12 @@ SPACING_CLASSES = ("same_downstream", "same_upstream", "opposite_downstream", "o
 class CentralityStruct(C.Structure):
     _fields_ = [("sites", C.c_uint64), ("max_offset", C.c_uint32), ("window", C.c_uint32), ("in_window", C.c_uint64),
                 ("expected", C.c_double), ("log10_pvalue", C.c_double), ("log10_evalue", C.c_double)]
+
+
+class DyadStruct(C.Structure):
+    _fields_ = [("gap", C.c_uint32), ("key", C.c_uint32), ("count", C.c_uint64), ("positions", C.c_uint64), ("p", C.c_double),
+                ("expected", C.c_double), ("log10_pvalue", C.c_double), ("log10_evalue", C.c_double),
+                ("other_gaps_mean", C.c_double), ("family", C.c_uint32), ("is_head", C.c_uint32)]
 
 
 class EnrichmentStruct(C.Structure):
@@ -197,6 +205,8 @@ def lib():
         L.pengk_centrality_histograms.argtypes = [vp, C.c_int, vp, vp, vp, u64, vp, vp, C.c_uint32, vp, vp]
         L.pengk_centrality_summary.argtypes = [vp, vp, C.c_uint32, C.c_int, C.c_int, C.POINTER(CentralityStruct)]
         L.pengk_binomial_log10_sf.argtypes = [u64, u64, C.c_double, C.POINTER(C.c_double)]
+        L.pengk_dyad_count.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, C.c_int, vp, vp]
+        L.pengk_dyad_summary.argtypes = [vp, vp, C.c_int, C.c_int, u64, C.c_double, vp, u64, C.POINTER(u64)]
         L.pengk_site_profiles.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, vp, vp, vp, vp, C.c_int, vp]
         L.pengk_profile_refine.argtypes = [vp, C.c_int, C.c_int, vp, C.c_double, vp, vp, vp, C.POINTER(C.c_int32),
                                            C.POINTER(C.c_int32), C.POINTER(u64)]
@@ -326,6 +336,25 @@ def binomial_log10_sf(n, k, p):
     out = C.c_double()
     _check(lib().pengk_binomial_log10_sf(int(n), int(k), float(p), C.byref(out)))
     return out.value
+
+
+def dyad_summary(counts, mono, both, min_count=5, max_evalue=0.01, capacity=None):
+    """the --dyads report from the summed tables of Context.dyad_count (pengk_dyad_summary, CPU): a list of dicts with
+    gap, key, count, positions, p, expected, log10_pvalue, log10_evalue, other_gaps_mean, family, is_head, in report
+    order.  capacity: the lines the first call has room for (a test hook: the call is repeated when there are more)."""
+    c = np.ascontiguousarray(counts, np.uint64)
+    m = np.ascontiguousarray(mono, np.uint64)
+    assert c.ndim == 2 and c.shape[1] == 4096 and m.shape == (64,)
+    n = C.c_uint64()
+    cap = 256 if capacity is None else int(capacity)
+    while True:
+        out = (DyadStruct * max(cap, 1))()
+        _check(lib().pengk_dyad_summary(c.ctypes.data, m.ctypes.data, c.shape[0] - 1, int(both), int(min_count), float(max_evalue),
+                                        C.addressof(out), cap, C.byref(n)))
+        if n.value <= cap:
+            break
+        cap = n.value
+    return [{k: getattr(out[i], k) for k, _ in DyadStruct._fields_} for i in range(n.value)]
 
 
 def hypergeom_log10_sf(N, K, n, k):
@@ -795,6 +824,19 @@ class Context:
                                                _ptr(scan[3]), scan[4] if n_seq is None else n_seq, int(threshold),
                                                _ptr(out_valid), _ptr(masked)))
         return out_valid, masked
+
+    # ---- spaced dyads (--dyads) -------------------------------------------------------------------------------
+    def dyad_count(self, scan, max_gap, both, all_valid=False, counts=None, mono=None, n_seq=None):
+        """(counts, mono), both on the device: the (max_gap + 1) x 4096 dyad table and the 64 triplet counts of `scan`
+        (pengk_dyad_count).  all_valid: d_valid = NULL.  counts / mono: device uint64 arrays to ADD to instead of fresh
+        zeroed ones.  n_seq: another count than scan[4] (argument tests)."""
+        if counts is None:
+            counts = self.to_device(np.zeros((max(0, min(int(max_gap), DYAD_MAX_GAP)) + 1, 4096), np.uint64))
+        if mono is None:
+            mono = self.to_device(np.zeros(64, np.uint64))
+        _check(lib().pengk_dyad_count(self.h, _ptr(scan[0]), None if all_valid else _ptr(scan[1]), _ptr(scan[2]), _ptr(scan[3]),
+                                      scan[4] if n_seq is None else n_seq, int(max_gap), int(both), _ptr(counts), _ptr(mono)))
+        return counts, mono
 
     def pack_scan(self, scan, W, item_windows=0, valid=None, all_valid=False, attach=False):
         """the sequences of `scan` (under the validity words `valid` instead of its own, when given) in the count layout,

@@ -87,6 +87,13 @@ double Global::holdoutFraction = 0.1;
 unsigned long long Global::holdoutThreshold = 0;
 unsigned long long Global::holdoutSeed = 1;   // (--score-seed's default)
 double Global::holdoutPvalue = 1e-3;          // (--enrich-pvalue's default)
+char* Global::dyadsFilename = nullptr;
+int Global::dyadsMaxGap = 20;
+double Global::dyadsEvalue = 0.01;
+unsigned long long Global::dyadsMinCount = 5;
+char* Global::dyadsMotifsFilename = nullptr;
+int Global::dyadsTop = 5;
+double Global::dyadsPvalue = 1e-3;  // (an exact six-letter match has p = 4^-6 = 2.4e-4: --refine's 1e-4 would find no site)
 bool Global::discriminative = false;
 double Global::discriminativePseudocount = 1.0;
 bool Global::scoreNegativesControl = false;
@@ -110,7 +117,8 @@ void Global::init(int nargs, char* args[]) {
   // (the scoring, the sites, the centrality, the refinement, the spacing, the first-order models and the database
   // enrichment scan the input after the motifs are found)
   pengk_host::keep_host_codes(scoreMotifs || sitesFilename || centralityFilename || refineFilename || spacingFilename ||
-                              dinucFilename || enrichFilename || eraseFilename || maskLowComplexity || holdoutFilename);
+                              dinucFilename || enrichFilename || eraseFilename || maskLowComplexity || holdoutFilename ||
+                              dyadsFilename);
   // both strands are handled inside the count; sequences are always read single stranded
   // ... and every chunk of the input set is packed and sent to the device while the rest is still being read
   pengk_host::begin_streaming_pack(patternLength);
@@ -199,6 +207,7 @@ void Global::readArguments(int nargs, char* args[]) {
   inputSequenceFilename = args[1];
   const char* holdout_option = nullptr;  // the last option given that only means something with --holdout
   const char* mask_option = nullptr;  // the last option given that only means something with --mask-low-complexity
+  const char* dyads_option = nullptr;  // ... with --dyads
   for (int i = 2; i < nargs; i++) {
     const char* a = args[i];
     if (!strcmp(a, "-w")) {
@@ -522,6 +531,42 @@ void Global::readArguments(int nargs, char* args[]) {
         exit(4);
       }
       holdout_option = "--holdout-pvalue";
+    } else if (!strcmp(a, "--dyads")) {
+      dyadsFilename = (char*)need(i, nargs, args, printHelp);
+    } else if (!strcmp(a, "--dyads-motifs")) {
+      dyadsMotifsFilename = (char*)need(i, nargs, args, printHelp);
+      dyads_option = "--dyads-motifs";
+    } else if (!strcmp(a, "--dyads-max-gap") || !strcmp(a, "--dyads-min-count") || !strcmp(a, "--dyads-top")) {
+      const int which = !strcmp(a, "--dyads-max-gap") ? 0 : !strcmp(a, "--dyads-min-count") ? 1 : 2;
+      static const char* const kName[3] = {"--dyads-max-gap", "--dyads-min-count", "--dyads-top"};
+      static const char* const kRange[3] = {"--dyads-max-gap must be an integer in [0, 26]",
+                                            "--dyads-min-count must be an integer in [1, 1000000000]",
+                                            "--dyads-top must be an integer in [1, 64]"};
+      const long long lo = which == 0 ? 0 : 1, hi = which == 0 ? PENGK_DYAD_MAX_GAP : which == 1 ? 1000000000ll : 64;
+      const char* v = need(i, nargs, args, printHelp);
+      char* end = nullptr;
+      const long long n = std::strtoll(v, &end, 10);
+      if (end == v || *end || n < lo || n > hi) {
+        printHelp();
+        log_line("ERROR", kRange[which]);
+        exit(4);
+      }
+      if (which == 0) dyadsMaxGap = (int)n;
+      else if (which == 1) dyadsMinCount = (unsigned long long)n;
+      else dyadsTop = (int)n;
+      dyads_option = kName[which];
+    } else if (!strcmp(a, "--dyads-evalue") || !strcmp(a, "--dyads-pvalue")) {
+      const bool ev = !strcmp(a, "--dyads-evalue");
+      const char* v = need(i, nargs, args, printHelp);
+      char* end = nullptr;
+      const double x = std::strtod(v, &end);
+      if (end == v || *end || !(x > 0.0) || (ev ? !(x <= 1e300) : !(x <= 1.0))) {
+        printHelp();
+        log_line("ERROR", ev ? "--dyads-evalue must be a positive number" : "--dyads-pvalue must be a number in (0, 1]");
+        exit(4);
+      }
+      (ev ? dyadsEvalue : dyadsPvalue) = x;
+      dyads_option = ev ? "--dyads-evalue" : "--dyads-pvalue";
     } else if (!strcmp(a, "--discriminative")) {
       discriminative = true;
     } else if (!strcmp(a, "--discriminative-pseudocount")) {
@@ -582,6 +627,11 @@ void Global::readArguments(int nargs, char* args[]) {
     exit(4);
   }
   holdoutThreshold = (unsigned long long)(holdoutFraction * 4294967296.0);
+  if (dyads_option && !dyadsFilename) {
+    printHelp();
+    log_line("ERROR", std::string(dyads_option) + " requires --dyads");
+    exit(4);
+  }
   if (mask_option && !maskLowComplexity) {
     printHelp();
     log_line("ERROR", std::string(mask_option) + " requires --mask-low-complexity");
@@ -640,6 +690,17 @@ void Global::printHelp() {
   printf("  --holdout-fraction FLOAT       the share set aside, in (0, 0.5] (default 0.1)\n");
   printf("  --holdout-seed INT             seed of the split (default 1)\n");
   printf("  --holdout-pvalue FLOAT         per-window p-value of the lowest score threshold tried, in (0, 1] (default 1e-3)\n");
+  printf("  --dyads FILE                   count every pair of trinucleotides 0 .. --dyads-max-gap unconstrained bases apart over\n");
+  printf("                                 what round 1 counts, test each against the product of the triplet frequencies\n");
+  printf("                                 (binomial, E-value over all pairs and gaps) and fold shifted neighbours into\n");
+  printf("                                 families: the bipartite sites of dimeric factors (CGG n11 CCG), which no\n");
+  printf("                                 contiguous word holds.  FILE: one line per dyad, tab-separated\n");
+  printf("  --dyads-max-gap INT            largest spacer counted, 0..26 (default 20)\n");
+  printf("  --dyads-evalue FLOAT           a dyad is reported at this E-value or below (default 0.01)\n");
+  printf("  --dyads-min-count INT          occurrences a dyad needs (default 5)\n");
+  printf("  --dyads-motifs FILE            the first family heads refined from their sites as --refine does it, as MEME\n");
+  printf("  --dyads-top INT                family heads refined, 1..64 (default 5)\n");
+  printf("  --dyads-pvalue FLOAT           p-value threshold of a site in that refinement, in (0, 1] (default 1e-3)\n");
   printf("  --erase FILE                   after the search, mask the sites of the motifs found and search what is left\n");
   printf("                                 again; the later rounds' motifs are appended.  FILE: one line per round and motif\n");
   printf("  --erase-rounds INT             further rounds of --erase, 1..8 (default 1); a round that finds or erases\n");

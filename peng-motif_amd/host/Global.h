@@ -103,6 +103,13 @@ class Global {
   static unsigned long long holdoutThreshold; // ... as the split's threshold: (uint64_t)(fraction * 2^32)
   static unsigned long long holdoutSeed;     // --holdout-seed
   static double holdoutPvalue;               // --holdout-pvalue: the floor of the score thresholds tried
+  static char* dyadsFilename;                // --dyads (new: spaced trinucleotide pairs counted on the device)
+  static int dyadsMaxGap;                    // --dyads-max-gap: 0..PENGK_DYAD_MAX_GAP
+  static double dyadsEvalue;                 // --dyads-evalue
+  static unsigned long long dyadsMinCount;   // --dyads-min-count
+  static char* dyadsMotifsFilename;          // --dyads-motifs: the refined family heads as MEME
+  static int dyadsTop;                       // --dyads-top: family heads refined
+  static double dyadsPvalue;                 // --dyads-pvalue: site threshold of that refinement
   static bool discriminative;                // --discriminative (new: the k-mer sweep held to the control set's counts)
   static double discriminativePseudocount;   // --discriminative-pseudocount
   static bool scoreNegativesControl;         // --score-negatives control (new: the --background-sequences file as negatives, matched to the input)

@@ -18,6 +18,7 @@
 #include "motif_compare.h"
 #include "motif_dinuc.h"
 #include "motif_dust.h"
+#include "motif_dyads.h"
 #include "motif_enrich.h"
 #include "motif_erase.h"
 #include "motif_holdout.h"
@@ -123,6 +124,26 @@ int main(int nargs, char** args) {
     clock.lap("holdout split");
   }
   const ScanSubset training = holdout.input.share(0);
+  // --dyads: spaced trinucleotide pairs over what round 1 counts -- the training share, behind the mask
+  if (Global::dyadsFilename && Global::patternLength >= PENGK_MIN_W && Global::patternLength <= PENGK_MAX_W) {
+    if (!scan) {
+      scan.reset(new ScanInput);
+      build_scan_input(*Global::inputSequenceSet, scan.get());
+    }
+    DyadSettings ds;
+    ds.max_gap = Global::dyadsMaxGap;
+    ds.evalue = Global::dyadsEvalue;
+    ds.min_count = Global::dyadsMinCount;
+    ds.top = Global::dyadsTop;
+    ds.pvalue = Global::dyadsPvalue;
+    RefineSettings rs;
+    rs.flank = Global::refineFlank;
+    rs.iterations = Global::refineIterations;
+    rs.min_ic = Global::refineMinIC;
+    write_dyads(*Global::inputSequenceSet, *scan, lc_mask.erase_valid(), holdout.attached ? &training : nullptr, *bgModel,
+                Global::strand == Strand::BOTH_STRANDS, ds, rs, Global::dyadsFilename, Global::dyadsMotifsFilename);
+    clock.lap("dyads");
+  }
   Peng peng(Global::strand, Global::bgModelOrder, Global::maxOptBgModelOrder, Global::inputSequenceSet, bgModel);
 
   PengParameters params;

@@ -10,39 +10,22 @@
 #include "device.h"
 #include "shared/Alphabet.h"
 
-namespace {
-struct Refined {
-  std::vector<float> pwm;  // w x 4, the matrix of the next round
-  int w = 0;
-  int left = 0, right = 0;  // columns gained on either side of the found PWM (negative: trimmed)
-  int rounds = 0;           // rounds that gave a matrix
-  long long sites = 0;      // sequences with a site in the last of them
-  bool active = true;
-  bool have_prev = false;
-  int prev_first = 0, prev_last = 0;  // the last round's kept range, in the found PWM's columns
-  std::vector<long long> prev_counts;
-};
-}  // namespace
-
-void write_refined_motifs(const std::vector<IUPACPattern*>& pats, SequenceSet& set, const ScanInput& in, BackgroundModel& bg,
-                          bool both_strands, const RefineSettings& rs, const std::string& path) {
+std::vector<RefinedMotif> refine_matrices(const std::vector<std::vector<float>>& start, SequenceSet& set, const ScanInput& in,
+                                          BackgroundModel& bg, bool both_strands, const RefineSettings& rs) {
   using pengk_host::check;
   using pengk_host::DeviceBuffer;
-  pengk_host::Lap lap("  refine: ");
-  const int n_motifs = (int)pats.size();
+  typedef RefinedMotif Refined;
+  const int n_motifs = (int)start.size();
   const size_t n_local = in.n_local;
   const float* bg0 = bg.getV()[0];
   const size_t ROW = (size_t)PENGK_MAX_MOTIF_LEN * 4, BINS = (size_t)PENGK_MAX_MOTIF_LEN * 5;
 
-  // round 0 starts from the found PWMs (as --sites and --centrality scan them)
+  // round 0 starts from the matrices as they are given (as --sites and --centrality scan the found PWMs)
   std::vector<Refined> mot(n_motifs);
-  std::vector<int32_t> S, len;
-  motif_log_odds(pats, bg0, S, len, "motif refinement");
+  std::vector<int32_t> S((size_t)std::max(n_motifs, 1) * ROW, 0), len(std::max(n_motifs, 1), 0);
   for (int m = 0; m < n_motifs; ++m) {
-    mot[m].w = len[m];
-    mot[m].pwm.resize((size_t)len[m] * 4);
-    for (int j = 0; j < len[m]; ++j)
-      for (int a = 0; a < 4; ++a) mot[m].pwm[(size_t)j * 4 + a] = pats[m]->get_pwm()[j][a];
+    mot[m].w = mot[m].w0 = (int)(start[m].size() / 4);
+    mot[m].pwm = start[m];
   }
 
   pengk_ctx* ctx = pengk_host::context();
@@ -112,14 +95,16 @@ void write_refined_motifs(const std::vector<IUPACPattern*>& pats, SequenceSet& s
       r.w = last - first;
       r.pwm.assign(pwm, pwm + (size_t)r.w * 4);
       r.left = -a;
-      r.right = b - (int)pats[m]->get_pattern_length();
+      r.right = b - r.w0;
       r.rounds += 1;
       r.sites = (long long)sites;
     }
   }
-  lap("rounds");
-  if (pengk_host::rank() != 0) return;
+  return mot;
+}
 
+void write_refined_meme(const std::vector<RefinedMotif>& mot, const std::vector<std::string>& names, const float* bg0,
+                        const std::string& path) {
   FILE* f = fopen(path.c_str(), "wb");
   if (!f) {
     std::cerr << "Unable to open output file (" << path << ")!" << std::endl;
@@ -135,11 +120,11 @@ void write_refined_motifs(const std::vector<IUPACPattern*>& pats, SequenceSet& s
   head << std::endl << std::endl;
   std::string o = head.str();
   char line[256];
-  for (int m = 0; m < n_motifs; ++m) {
-    const Refined& r = mot[m];
+  for (size_t m = 0; m < mot.size(); ++m) {
+    const RefinedMotif& r = mot[m];
     snprintf(line, sizeof line, "letter-probability matrix: alength= 4 w= %d nsites= %lld iterations= %d left= %d right= %d\n", r.w,
              r.sites, r.rounds, r.left, r.right);
-    o += "MOTIF " + pats[m]->get_pattern_string() + "\n" + line;
+    o += "MOTIF " + names[m] + "\n" + line;
     for (int j = 0; j < r.w; ++j) {
       const float* q = &r.pwm[(size_t)j * 4];
       snprintf(line, sizeof line, "%.8f %.8f %.8f %.8f\n", (double)q[0], (double)q[1], (double)q[2], (double)q[3]);
@@ -152,5 +137,25 @@ void write_refined_motifs(const std::vector<IUPACPattern*>& pats, SequenceSet& s
     std::cerr << "Error: writing " << path << " failed" << std::endl;
     exit(1);
   }
+}
+
+void write_refined_motifs(const std::vector<IUPACPattern*>& pats, SequenceSet& set, const ScanInput& in, BackgroundModel& bg,
+                          bool both_strands, const RefineSettings& rs, const std::string& path) {
+  pengk_host::Lap lap("  refine: ");
+  const float* bg0 = bg.getV()[0];
+  std::vector<int32_t> S, len;
+  motif_log_odds(pats, bg0, S, len, "motif refinement");  // (a motif wider than PENGK_MAX_MOTIF_LEN ends the program here)
+  std::vector<std::vector<float>> start(pats.size());
+  std::vector<std::string> names(pats.size());
+  for (size_t m = 0; m < pats.size(); ++m) {
+    start[m].resize((size_t)len[m] * 4);
+    for (int j = 0; j < len[m]; ++j)
+      for (int a = 0; a < 4; ++a) start[m][(size_t)j * 4 + a] = pats[m]->get_pwm()[j][a];
+    names[m] = pats[m]->get_pattern_string();
+  }
+  const std::vector<RefinedMotif> mot = refine_matrices(start, set, in, bg, both_strands, rs);
+  lap("rounds");
+  if (pengk_host::rank() != 0) return;
+  write_refined_meme(mot, names, bg0, path);
   lap("written");
 }

@@ -19,6 +19,27 @@ struct RefineSettings {
   double min_ic = 0.25;  // --refine-min-ic: bits the outermost kept columns need
 };
 
+// One motif as the rounds leave it.
+struct RefinedMotif {
+  std::vector<float> pwm;  // w x 4, the matrix of the next round
+  int w = 0;
+  int w0 = 0;               // the width it started with
+  int left = 0, right = 0;  // columns gained on either side of the starting matrix (negative: trimmed)
+  int rounds = 0;           // rounds that gave a matrix
+  long long sites = 0;      // sequences with a site in the last of them
+  bool active = true;
+  bool have_prev = false;
+  int prev_first = 0, prev_last = 0;  // the last round's kept range, in the starting matrix's columns
+  std::vector<long long> prev_counts;
+};
+// The rounds described below from any starting matrices (start[m]: w x 4 probabilities, 1 <= w <= PENGK_MAX_MOTIF_LEN):
+// what --refine runs on the found PWMs and --dyads-motifs on the family heads.  Collective in a multi-rank run.
+std::vector<RefinedMotif> refine_matrices(const std::vector<std::vector<float>>& start, SequenceSet& set, const ScanInput& in,
+                                          BackgroundModel& bg, bool both_strands, const RefineSettings& rs);
+// ... and the MEME file of the result under the given motif names (the caller's rank 0 calls it)
+void write_refined_meme(const std::vector<RefinedMotif>& mot, const std::vector<std::string>& names, const float* bg0,
+                        const std::string& path);
+
 // Refines pats (in their order: the MEME file's; the patterns themselves stay as they are) over this rank's records of
 // `set` (scan layout `in`) and writes them to `path` as a MEME file.  Per round and motif: integer log-odds and the
 // threshold at `pvalue` under the order-0 background V[0] of bg, the best window strand of every sequence, the base
