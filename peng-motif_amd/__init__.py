@@ -577,6 +577,17 @@ class Context:
     def synchronize(self):
         _check(lib().pengk_synchronize(self.h))
 
+    def stream(self):
+        """the hipStream_t the context enqueues on, as an int (pengk_stream; 0 = the null stream)"""
+        return int(lib().pengk_stream(self.h) or 0)
+
+    def set_stream(self, s):
+        """re-target the context to a caller-owned stream (pengk_set_stream; waits for the work pending on the old one):
+        a torch.cuda.Stream, a hipStream_t as an int, or None / 0 for the null stream.  The caller keeps the stream alive."""
+        if s is not None and hasattr(s, "cuda_stream"):
+            s = s.cuda_stream
+        _check(lib().pengk_set_stream(self.h, C.c_void_p(int(s) if s else 0)))
+
     def set_option(self, name, value):
         _check(lib().pengk_set_option(self.h, name.encode(), int(value)))
 
