@@ -1425,15 +1425,6 @@ __global__ __launch_bounds__(128) void bg_model_kernel(const unsigned long long*
 // ---------------------------------------------------------------------------------------------
 // Synthetic input written directly in the packed layout.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {
-  x ^= x >> 30;
-  x *= 0xBF58476D1CE4E5B9ull;
-  x ^= x >> 27;
-  x *= 0x94D049BB133111EBull;
-  x ^= x >> 31;
-  return x;
-}
-
 __global__ __launch_bounds__(256) void synth_words_kernel(uint64_t seed, uint64_t seq0, uint64_t n_seq, uint32_t L,
                                                           uint64_t* __restrict__ words, uint64_t n_words) {
   const uint64_t motif = 2ull | (1ull << 2) | (3ull << 4) | (2ull << 6) | (0ull << 8) | (2ull << 10) | (3ull << 12) |

@@ -1,6 +1,6 @@
 // erase.hip -- masking the sites of found motifs and packing what is left, on the device (--erase).
 //
-//   mask     the sites walk of score.hip once more (scan_walk.h), with a visitor that turns every site into cover bits:
+//   mask     the sites walk of sites.hip once more (scan_walk.h), with a visitor that turns every site into cover bits:
 //            d_out_valid = d_valid & ~cover.  Windows arrive in ascending position, so a "covered until" index and one
 //            pending word per thread are all the state; a word's cover is ANDed out with one integer atomic, whose
 //            returned old value says which bits this call cleared first (the erased count).  Integer AND commutes:
@@ -107,12 +107,10 @@ __global__ __launch_bounds__(SCAN_THREADS) void mask_sites_kernel(const uint64_t
   __shared__ unsigned long long msites[SCAN_MAX_MOTIFS];
   __shared__ unsigned long long berased;
   const GroupRec g = groups[blockIdx.y];
-  for (int t = threadIdx.x; t < g.n_ints; t += SCAN_THREADS) tab[t] = tables[g.table0 + t];
-  for (int t = threadIdx.x; t < g.m1 - g.m0; t += SCAN_THREADS) {
-    mrec[t] = recs[g.m0 + t];
-    mthr[t] = thr[recs[g.m0 + t].m];
+  load_group(g, tables, recs, tab, mrec, [&](int t, const MotifRec& mr) {
+    mthr[t] = thr[mr.m];
     msites[t] = 0;
-  }
+  });
   if (threadIdx.x == 0) berased = 0;
   __syncthreads();
   unsigned long long mine = 0;

@@ -135,6 +135,17 @@ __host__ __device__ inline uint32_t revcomp32(uint32_t id, int W) {
   return v >> (32 - 2 * W);
 }
 
+// The splitmix64 finalizer: every counter-based draw of the library (the synthetic inputs, the background sampler, the
+// best-site tie-break keys, the hold-out split).
+__host__ __device__ __forceinline__ uint64_t mix64(uint64_t x) {
+  x ^= x >> 30;
+  x *= 0xBF58476D1CE4E5B9ull;
+  x ^= x >> 27;
+  x *= 0x94D049BB133111EBull;
+  x ^= x >> 31;
+  return x;
+}
+
 // launchers implemented in the .hip files
 int launch_count(pengk_ctx* ctx, int both, uint32_t* d_counts, uint64_t* d_ltot, uint64_t* d_bg /* may be NULL */);
 int launch_mirror(pengk_ctx* ctx, int W, uint32_t* d_counts);

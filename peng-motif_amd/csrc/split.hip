@@ -25,16 +25,6 @@ constexpr int SPLIT_WAVE_SPAN = 64 * SPLIT_ROUNDS;         // ... a wave's conse
 constexpr int SPLIT_TILE = SPLIT_THREADS * SPLIT_ROUNDS;   // ... and a workgroup's
 constexpr int SPLIT_SCAN_PER = 8;
 
-// the splitmix64 finalizer (score.hip's mix64, restated)
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {
-  x ^= x >> 30;
-  x *= 0xBF58476D1CE4E5B9ull;
-  x ^= x >> 27;
-  x *= 0x94D049BB133111EBull;
-  x ^= x >> 31;
-  return x;
-}
-
 // Element e of tile b is sequence b * SPLIT_TILE + e; wave w of the workgroup owns elements [w * SPLIT_WAVE_SPAN,
 // + SPLIT_WAVE_SPAN) and takes them 64 at a time, lane by lane: file order is (tile, wave, round, lane).
 __device__ __forceinline__ uint64_t split_seq(uint32_t round) {

@@ -22,7 +22,7 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
-SCAN_TABLES, PRIV_BINS = 40, 2560  # csrc/score.hip
+SCAN_TABLES, PRIV_BINS = 40, 2560  # csrc/scan_walk.h, csrc/sites.hip
 BG = np.full(4, 0.25, np.float32)
 
 

@@ -24,7 +24,7 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
-SCAN_TABLES, PRIV_BINS, LONG_SEQ = 40, 2560, 1 << 16  # csrc/score.hip
+SCAN_TABLES, PRIV_BINS, LONG_SEQ = 40, 2560, 1 << 16  # csrc/scan_walk.h, csrc/sites.hip
 BG = np.full(4, 0.25, np.float32)
 
 

@@ -1,4 +1,4 @@
-"""The sequence-scan kernels of csrc/score.hip (scan, sampler, synthetic generator, histograms, sites and their
+"""The sequence-scan kernels of csrc/score.hip, csrc/sites.hip and csrc/site_stats.hip (scan, sampler, synthetic generator, histograms, sites and their
 exclusive scan, best sites, centrality histograms, site profiles) compared value by value at the sizes the per-feature
 modules (test_gpu_motif_score / _sites / _centrality / _refine) only sum over: more sequences than one trip of a
 grid-stride loop, more scan elements than one pass of xscan_parts_kernel, many blocks and slices of
@@ -26,7 +26,7 @@ from test_gpu_motif_sites import random_S, random_seqs, thresholds
 
 pytestmark = pytest.mark.gpu
 
-SCAN_THREADS, XS_TILE, HIST_LDS_BINS, SCAN_TABLES = 256, 2048, 16384, 40  # csrc/score.hip
+SCAN_THREADS, XS_TILE, HIST_LDS_BINS, SCAN_TABLES = 256, 2048, 16384, 40  # csrc/scan_walk.h, csrc/sites.hip, csrc/score.hip
 CLASSES = np.array([20, 31, 32, 33, 47, 65])
 CLASS_P = [0.2, 0.2, 0.2, 0.2, 0.15, 0.05]
 BIG_SEQ0 = 2 ** 40 + 987654321  # GOLDEN * (g + 1) wraps many times over
