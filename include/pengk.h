@@ -745,6 +745,62 @@ typedef struct {
 int pengk_dyad_summary(const uint64_t* h_counts, const uint64_t* h_mono, int max_gap, int both_strands, uint64_t min_count,
                        double max_evalue, pengk_dyad* out, uint64_t capacity, uint64_t* n_out);
 
+/* ---- positional words (--positional: k-mers that keep one position in the sequences -- a TATA box 30 bases ahead of a
+ *      TSS, an Inr, a Kozak or splice-site signal, a weak site at a ChIP summit -- whether or not they are over-represented;
+ *      the question RSAT's position-analysis answers) ---------------------------------------------------
+ * This project's own definitions, integer up to the summary: a numpy restatement and any sharding give the same table.
+ * The numbers are NOT promised to be RSAT's.  Per sequence of the scan layout above, letters s[0..L) and validity bits v
+ * (d_valid = NULL: every base valid), r[p] = the number of consecutive valid bases from p on, K in 4 .. 7:
+ *   word        one stands at p iff r[p] >= K; its value has the first base highest (as the dyad key); key = the value, with
+ *               both_strands min(value, revcomp(value))
+ *   clump head  the occurrence at p is counted iff no word with the same key stands at any of p-1 .. p-(K-1).  A
+ *               predecessor cut by an invalid base, or before the sequence start, does not stand.  A run of 70 000 equal
+ *               letters counts once; ACACAC... counts its first two positions
+ *   coordinate  anchor 0 (start): c = p;  1 (end): c = L - K - p;  2 (centre): c = |2p + K - L| >> 1 -- unsigned, so the
+ *               answer is the same whichever strand a peak was written on
+ *   bin         b = c / bin_size; counted iff b < n_bins (words further out are ignored)
+ *   count       d_counts[b * 4^K + key] += 1
+ * d_counts (n_bins x 4^K uint64) is ADDED to (caller-zeroed): shards and several calls sum exactly.  No entry that is not
+ * canonical is ever written.  n_seq = 0 does nothing.  PENGK_ERR_ARG: K outside 4 .. 7, anchor outside 0 .. 2, bin_size
+ * outside 1 .. PENGK_POSITION_MAX_BIN_SIZE, n_bins outside 1 .. PENGK_POSITION_MAX_BINS, both_strands other than 0 / 1,
+ * n_seq >= 2^32, a null pointer (but d_valid) with n_seq > 0.  Asynchronous on the context's stream. */
+#define PENGK_POSITION_MIN_K 4
+#define PENGK_POSITION_MAX_K 7
+#define PENGK_POSITION_MAX_BINS 64
+#define PENGK_POSITION_MAX_BIN_SIZE 65536
+int pengk_position_count(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_valid, const int64_t* d_offs,
+                         const uint32_t* d_lens, uint64_t n_seq, int K, int anchor, int bin_size, int n_bins, int both_strands,
+                         uint64_t* d_counts /* n_bins x 4^K, ADDED to */);
+typedef struct {
+  uint32_t key;              /* the word, first base highest (the canonical one on both strands) */
+  uint32_t bin;              /* b: the key's best bin */
+  uint64_t count;            /* d_counts[b * 4^K + key] */
+  uint64_t total;            /* C[key]: the key's count over all bins */
+  uint64_t bin_positions;    /* N[b]: the sum of row b */
+  double expected;           /* (double)C[key] * q[b] */
+  double log10_pvalue;       /* log10 P(X >= count), X ~ Binomial(C[key], q[b]) */
+  double log10_evalue;       /* log10_pvalue + log10(tests) */
+  uint32_t bins_significant; /* the key's candidate bins at or below max_evalue */
+  uint32_t family;           /* the 1-based rank of the family's head */
+  uint32_t is_head;          /* 1 for the head itself */
+} pengk_position_word;
+/* Pure CPU.  The report from the table of pengk_position_count (summed over all ranks), in this order.  N[b] = the integer
+ * sum of row b, C[key] = the integer sum of the key's column, Nt = the sum of all N, q[b] = (double)N[b] / (double)Nt;
+ * keys = 4^K on one strand, on both 4^K / 2 for odd K and (4^K + 4^(K/2)) / 2 for even K (2080 at K = 6);
+ * tests = n_bins * keys.  A (key, b) is a candidate iff count >= min_count and (double)count > (double)C[key] * q[b]
+ * (depleted positions are not reported); log10_pvalue = pengk_binomial_log10_sf(C[key], count, q[b]), log10_evalue =
+ * log10_pvalue + log10((double)tests).  A key's line carries its best bin -- the smallest log10_evalue, on a tie the
+ * lowest bin -- and bins_significant, the number of its candidate bins with log10_evalue <= log10(max_evalue).  Keys whose
+ * best bin is at or below that are reported, ordered by (log10_evalue, bin, key) ascending.
+ * Families: walking the report in order, a word joins the first earlier family head whose best bin differs by at most 1
+ * from its own and to which it is related, else it heads a new family.  Y is related to X iff for some offset o in
+ * -2 .. 2, Y laid at o on X has no column where the letters differ and at least 4 columns where they are the same; on both
+ * strands Y's reverse complement is tried as well.
+ * Only the first `capacity` lines are written to `out`; *n_out is always the full count, so a caller with too small an
+ * array calls again.  Nt = 0 reports nothing.  PENGK_ERR_ARG: K, n_bins or both_strands as above, max_evalue not > 0. */
+int pengk_position_summary(const uint64_t* h_counts, int K, int n_bins, int both_strands, uint64_t min_count, double max_evalue,
+                           pengk_position_word* out, uint64_t capacity, uint64_t* n_out);
+
 /* ---- motif refinement (--refine: the found motifs re-estimated and extended from their sites, as MEME, HOMER and STREME
  *      end) -------------------------------------------------------------------------------------------
  * Over the scan layout and the best sites of pengk_motif_best_sites.  Integer up to the counts: any slicing, any rank

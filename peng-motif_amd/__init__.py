@@ -41,6 +41,7 @@ EXPORTS = [
     "pengk_motif_enrich", "pengk_hypergeom_log10_sf", "pengk_enrich_summary",
     "pengk_motif_best_sites", "pengk_centrality_histograms", "pengk_centrality_summary", "pengk_binomial_log10_sf",
     "pengk_dyad_count", "pengk_dyad_summary",
+    "pengk_position_count", "pengk_position_summary",
     "pengk_site_profiles", "pengk_profile_refine",
     "pengk_site_pair_profiles", "pengk_dinuc_model", "pengk_motif_scan_dinuc",
     "pengk_spacing_histograms", "pengk_spacing_summary",
@@ -52,6 +53,10 @@ SITES_BLOCK = 4096
 SITE = np.dtype([("seq", np.uint32), ("pos", np.uint32), ("score", np.int32), ("motif_strand", np.uint32)])
 CENTRALITY_MAX_LEN = 65536
 DYAD_MAX_GAP = 26
+POSITION_MIN_K, POSITION_MAX_K = 4, 7
+POSITION_MAX_BINS = 64
+POSITION_MAX_BIN_SIZE = 65536
+POSITION_ANCHORS = ("start", "end", "center")
 SPACING_MAX_MOTIFS = 64
 SPACING_MAX_GAP = 1024
 COMPARE_BINS = 257
@@ -67,6 +72,12 @@ class DyadStruct(C.Structure):
     _fields_ = [("gap", C.c_uint32), ("key", C.c_uint32), ("count", C.c_uint64), ("positions", C.c_uint64), ("p", C.c_double),
                 ("expected", C.c_double), ("log10_pvalue", C.c_double), ("log10_evalue", C.c_double),
                 ("other_gaps_mean", C.c_double), ("family", C.c_uint32), ("is_head", C.c_uint32)]
+
+
+class PositionWordStruct(C.Structure):
+    _fields_ = [("key", C.c_uint32), ("bin", C.c_uint32), ("count", C.c_uint64), ("total", C.c_uint64),
+                ("bin_positions", C.c_uint64), ("expected", C.c_double), ("log10_pvalue", C.c_double),
+                ("log10_evalue", C.c_double), ("bins_significant", C.c_uint32), ("family", C.c_uint32), ("is_head", C.c_uint32)]
 
 
 class EnrichmentStruct(C.Structure):
@@ -207,6 +218,8 @@ def lib():
         L.pengk_binomial_log10_sf.argtypes = [u64, u64, C.c_double, C.POINTER(C.c_double)]
         L.pengk_dyad_count.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, C.c_int, vp, vp]
         L.pengk_dyad_summary.argtypes = [vp, vp, C.c_int, C.c_int, u64, C.c_double, vp, u64, C.POINTER(u64)]
+        L.pengk_position_count.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
+        L.pengk_position_summary.argtypes = [vp, C.c_int, C.c_int, C.c_int, u64, C.c_double, vp, u64, C.POINTER(u64)]
         L.pengk_site_profiles.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, vp, vp, vp, vp, C.c_int, vp]
         L.pengk_profile_refine.argtypes = [vp, C.c_int, C.c_int, vp, C.c_double, vp, vp, vp, C.POINTER(C.c_int32),
                                            C.POINTER(C.c_int32), C.POINTER(u64)]
@@ -355,6 +368,27 @@ def dyad_summary(counts, mono, both, min_count=5, max_evalue=0.01, capacity=None
             break
         cap = n.value
     return [{k: getattr(out[i], k) for k, _ in DyadStruct._fields_} for i in range(n.value)]
+
+
+def position_summary(counts, K, both, min_count=5, max_evalue=0.01, capacity=None):
+    """the --positional report from the summed table of Context.position_count (pengk_position_summary, CPU): a list of
+    dicts with key, bin, count, total, bin_positions, expected, log10_pvalue, log10_evalue, bins_significant, family,
+    is_head, in report order.  capacity: the lines the first call has room for (a test hook: the call is repeated when
+    there are more)."""
+    c = np.ascontiguousarray(counts, np.uint64)
+    assert c.ndim == 2
+    if POSITION_MIN_K <= int(K) <= POSITION_MAX_K:
+        assert c.shape[1] == 4 ** int(K)
+    n = C.c_uint64()
+    cap = 256 if capacity is None else int(capacity)
+    while True:
+        out = (PositionWordStruct * max(cap, 1))()
+        _check(lib().pengk_position_summary(c.ctypes.data, int(K), c.shape[0], int(both), int(min_count), float(max_evalue),
+                                            C.addressof(out), cap, C.byref(n)))
+        if n.value <= cap:
+            break
+        cap = n.value
+    return [{k: getattr(out[i], k) for k, _ in PositionWordStruct._fields_} for i in range(n.value)]
 
 
 def hypergeom_log10_sf(N, K, n, k):
@@ -848,6 +882,19 @@ class Context:
         _check(lib().pengk_dyad_count(self.h, _ptr(scan[0]), None if all_valid else _ptr(scan[1]), _ptr(scan[2]), _ptr(scan[3]),
                                       scan[4] if n_seq is None else n_seq, int(max_gap), int(both), _ptr(counts), _ptr(mono)))
         return counts, mono
+
+    # ---- positional words (--positional) ----------------------------------------------------------------------
+    def position_count(self, scan, K, anchor, bin_size, n_bins, both, all_valid=False, counts=None, n_seq=None):
+        """the n_bins x 4^K table of clump heads per position bin of `scan`, on the device (pengk_position_count).
+        anchor: 0 start, 1 end, 2 centre.  all_valid: d_valid = NULL.  counts: a device uint64 array to ADD to instead of
+        a fresh zeroed one.  n_seq: another count than scan[4] (argument tests)."""
+        if counts is None:
+            rows = max(1, min(int(n_bins), POSITION_MAX_BINS))
+            counts = self.to_device(np.zeros((rows, 4 ** max(POSITION_MIN_K, min(int(K), POSITION_MAX_K))), np.uint64))
+        _check(lib().pengk_position_count(self.h, _ptr(scan[0]), None if all_valid else _ptr(scan[1]), _ptr(scan[2]), _ptr(scan[3]),
+                                          scan[4] if n_seq is None else n_seq, int(K), int(anchor), int(bin_size), int(n_bins),
+                                          int(both), _ptr(counts)))
+        return counts
 
     def pack_scan(self, scan, W, item_windows=0, valid=None, all_valid=False, attach=False):
         """the sequences of `scan` (under the validity words `valid` instead of its own, when given) in the count layout,

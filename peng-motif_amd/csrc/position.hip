@@ -1,0 +1,454 @@
+// position.hip -- k-mers with a position bias counted on the device (--positional): the table defined in
+// include/pengk.h ("positional words").
+//
+//   tile     64 consecutive positions of one sequence, one wave, one position per lane.  A lane reads the 16 bases from
+//            q = max(p - (K-1), 0) on (its own word and the K-1 <= 6 words that may stand before it lie in the first
+//            2K-1 <= 13 of them: two 32-bit halves of the layout's words, one funnel shift) and the validity bits from q
+//            on; st = v & v>>1 & .. & v>>(K-1) says for every base of the window whether a word stands there.  Standing,
+//            clump head, coordinate and bin are decided in registers, in 32-bit arithmetic throughout.
+//   clumps   two words have the same key iff the code of one is the code of the other or, on both strands, its reverse
+//            complement: no predecessor is folded, each is compared with the lane's code and its reverse complement.
+//   groups   the position bins in groups of at most 2^15 / 4^K (64 at most); a workgroup owns one group (blockIdx.y) and
+//            keeps its tables in LDS, 4^K uint32 bins a position bin: 128 KiB at most.  Bins are bumped with non-returning
+//            LDS adds.  Inside a workgroup a word is its code as the words hold it (first base lowest), on both strands
+//            the smaller of the code and its reverse complement; the flush turns a bin's code into the public key (first
+//            base highest), folds it again in that order and adds the bin to the uint64 table with a plain vector atomic;
+//            empty bins add nothing, so no entry that is not canonical is ever written.
+//   tiles    only the tiles of a sequence that hold a position whose coordinate lies under bin_size * n_bins are walked:
+//            one contiguous range of them under every anchor (a superset is taken: the lane decides).  Their counts per
+//            sequence -> exclusive sums (two small launches), then every wave of a fixed grid takes one contiguous share
+//            of the tiles, as dyad.hip does: static, every wave of the grid runs the same number of rounds, so the
+//            barriers of the flush sit in workgroup-uniform control flow.  A tile none of whose positions can fall into
+//            the workgroup's bins is left before anything is loaded (one range of a sequence under start and end, two
+//            under centre).
+//   wrap     a position bumps at most one bin of a workgroup once, a round holds at most 1024 positions, and the tables are
+//            flushed every POS_FLUSH_ROUNDS = 2^21 rounds: no bin exceeds 2^31 between two flushes.
+// Nothing of size positions x bins is written to HBM.
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "pengk_internal.h"
+
+namespace pengk {
+namespace {
+
+constexpr int POS_THREADS = 1024;
+constexpr int POS_WAVES = POS_THREADS / 64;
+constexpr int POS_LDS_BINS = 1 << 15;            // uint32 bins a workgroup holds at most: 128 KiB
+constexpr uint32_t POS_FLUSH_ROUNDS = 1u << 21;  // x 1024 positions a round = 2^31 per bin at most
+constexpr int POS_SCAN_THREADS = 256;
+static_assert(POS_LDS_BINS * 4 <= 160 * 1024, "a group's tables fit in LDS");
+static_assert(2 * PENGK_POSITION_MAX_K - 1 <= 16, "a position's words lie in one window of 16 bases");
+static_assert((uint64_t)PENGK_POSITION_MAX_BIN_SIZE * PENGK_POSITION_MAX_BINS <= (1ull << 22), "the coordinates under test fit 32 bits");
+
+__host__ __device__ constexpr int pos_max_per_group(int K) {
+  return (POS_LDS_BINS >> (2 * K)) < PENGK_POSITION_MAX_BINS ? (POS_LDS_BINS >> (2 * K)) : PENGK_POSITION_MAX_BINS;
+}
+
+// the tiles of a sequence of L bases that may hold a position with a coordinate below R: nt of them from tile k0 on
+struct PosTiles {
+  uint32_t k0, nt;
+};
+__host__ __device__ __forceinline__ PosTiles pos_tiles(uint32_t L, int K, int anchor, uint32_t R) {
+  PosTiles t = {0u, 0u};
+  if (L < (uint32_t)K) return t;
+  const int64_t D = (int64_t)L - K;  // the last position
+  int64_t lo = 0, hi = D;
+  if (anchor == 0) {
+    hi = D < (int64_t)R - 1 ? D : (int64_t)R - 1;
+  } else if (anchor == 1) {
+    lo = D - ((int64_t)R - 1) > 0 ? D - ((int64_t)R - 1) : 0;
+  } else {  // |2p - D| < 2R: (D - 2R) / 2 < p < (D + 2R) / 2, rounded outwards
+    const int64_t a = (D - 2 * (int64_t)R) >> 1, b = (D + 2 * (int64_t)R + 1) >> 1;
+    lo = a > 0 ? a : 0;
+    hi = b < D ? b : D;
+  }
+  t.k0 = (uint32_t)(lo >> 6);
+  t.nt = (uint32_t)(hi >> 6) - t.k0 + 1u;
+  return t;
+}
+
+__device__ __forceinline__ uint32_t pos_valid_word(const uint32_t* vp, uint32_t L, uint32_t nw, uint32_t j) {
+  if (j >= nw) return 0u;
+  const uint32_t rem = L - 32u * j;
+  const uint32_t in = rem >= 32u ? 0xFFFFFFFFu : ((1u << rem) - 1u);
+  return vp ? vp[j] & in : in;
+}
+
+// ---- tile counts and their exclusive sums (the scheme of dyad.hip) ------------------------------------------------------
+__device__ __forceinline__ unsigned long long pos_group_inclusive_sum(unsigned long long v, unsigned long long* sh) {
+  const int t = threadIdx.x;
+  sh[t] = v;
+  __syncthreads();
+  for (int d = 1; d < POS_SCAN_THREADS; d <<= 1) {
+    const unsigned long long x = t >= d ? sh[t - d] : 0ull;
+    __syncthreads();
+    sh[t] += x;
+    __syncthreads();
+  }
+  const unsigned long long r = sh[t];
+  __syncthreads();
+  return r;
+}
+
+// excl[i]: the tiles of the sequences in front of i within its group of 256; boff[b]: the tiles of group b
+__global__ __launch_bounds__(POS_SCAN_THREADS) void pos_tiles_kernel(const uint32_t* __restrict__ lens, uint64_t n_seq, int K, int anchor,
+                                                                     uint32_t R, unsigned long long* __restrict__ excl,
+                                                                     unsigned long long* __restrict__ boff) {
+  __shared__ unsigned long long sh[POS_SCAN_THREADS];
+  const uint64_t i = (uint64_t)blockIdx.x * POS_SCAN_THREADS + threadIdx.x;
+  const unsigned long long nt = i < n_seq ? pos_tiles(lens[i], K, anchor, R).nt : 0u;
+  const unsigned long long incl = pos_group_inclusive_sum(nt, sh);
+  if (i < n_seq) excl[i] = incl - nt;
+  if (threadIdx.x == POS_SCAN_THREADS - 1) boff[blockIdx.x] = incl;
+}
+
+// boff[0 .. n_groups) -> exclusive sums in place, boff[n_groups] = the total; one workgroup
+__global__ __launch_bounds__(POS_SCAN_THREADS) void pos_groups_kernel(unsigned long long* __restrict__ boff, uint64_t n_groups) {
+  __shared__ unsigned long long sh[POS_SCAN_THREADS];
+  unsigned long long carry = 0;
+  for (uint64_t b = 0; b < n_groups; b += POS_SCAN_THREADS) {
+    const uint64_t k = b + threadIdx.x;
+    const unsigned long long v = k < n_groups ? boff[k] : 0ull;
+    const unsigned long long incl = pos_group_inclusive_sum(v, sh);
+    if (k < n_groups) boff[k] = carry + incl - v;
+    sh[threadIdx.x] = incl;  // (the last thread's is the chunk's total)
+    __syncthreads();
+    carry += sh[POS_SCAN_THREADS - 1];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) boff[n_groups] = carry;
+}
+
+// ---- the count ----------------------------------------------------------------------------------------------------------
+// the coordinate of position p <= D in a sequence whose last position is D.  32 bits throughout: with h = D >> 1 and
+// r = D & 1, |2p - D| >> 1 is h - p up to h and p - h - r behind it, and 2p is never formed
+__device__ __forceinline__ uint32_t pos_coordinate(int anchor, uint32_t p, uint32_t D) {
+  if (anchor == 0) return p;
+  if (anchor == 1) return D - p;
+  const uint32_t h = D >> 1, r = D & 1u;
+  return p > h ? p - h - r : h - p;
+}
+
+// One tile: the positions [64 k, 64 k + 64) of a sequence of L >= K bases whose words / validity words begin at wp / vp (vp
+// NULL: every base valid), under the coordinates [c0, c1) of this workgroup's bins; bins: its tables.
+template <int K, bool BOTH>
+__device__ __forceinline__ void pos_tile(const uint64_t* __restrict__ wp, const uint32_t* __restrict__ vp, uint32_t L, uint32_t k,
+                                         int anchor, uint32_t S, uint32_t c0, uint32_t c1, uint32_t* bins) {
+  constexpr uint32_t MASK = (1u << (2 * K)) - 1u;
+  const uint32_t D = L - (uint32_t)K;  // the last position
+  {  // (wave-uniform) can a position of the tile fall into [c0, c1)?  The coordinate is monotone on either side of the centre
+    const uint32_t P0 = k << 6;  // (k < 2^26)
+    if (P0 > D) return;
+    const uint32_t P1 = D - P0 < 63u ? D : P0 + 63u;
+    const uint32_t a = pos_coordinate(anchor, P0, D), b = pos_coordinate(anchor, P1, D);
+    const uint32_t most = a > b ? a : b;
+    uint32_t least = a < b ? a : b;
+    if (anchor == 2 && P0 <= (D >> 1) && (D >> 1) <= P1) least = 0u;
+    if (least >= c1 || most < c0) return;
+  }
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t p = (k << 6) + lane;  // (k < 2^26)
+  const uint32_t q = p >= (uint32_t)(K - 1) ? p - (uint32_t)(K - 1) : 0u;
+  const uint32_t off = p - q;  // the lane's own place in its window: K-1 but at the sequence's start
+  // the words as halves of 16 bases: the 2K-1 <= 13 bases from q on lie in the half of q and the next one
+  const uint32_t* hp = reinterpret_cast<const uint32_t*>(wp);
+  const uint32_t nh = (L + 15u) >> 4, h = q >> 4;
+  const uint32_t H0 = h < nh ? hp[h] : 0u, H1 = h + 1u < nh ? hp[h + 1u] : 0u;
+  const uint32_t lo = __builtin_amdgcn_alignbit(H1, H0, (q & 15u) << 1);  // the 16 bases from q on
+  const uint32_t nw = (L + 31u) >> 5, j = q >> 5;
+  const uint32_t V0 = pos_valid_word(vp, L, nw, j), V1 = pos_valid_word(vp, L, nw, j + 1u);
+  const uint32_t v = __builtin_amdgcn_alignbit(V1, V0, q & 31u);  // the validity bits of the 32 bases from q on
+  uint32_t st = v;  // bit i: a word stands at q + i
+#pragma unroll
+  for (int d = 1; d < K; ++d) st &= v >> d;
+  const uint32_t code = (lo >> (2u * off)) & MASK;
+  const uint32_t rc = BOTH ? revcomp32(code, K) : code;
+  bool on = (st >> off) & 1u;
+#pragma unroll
+  for (int d = 1; d < K; ++d) {  // an equal word standing at p - d: not a clump head
+    if ((uint32_t)d <= off) {
+      const uint32_t i = off - (uint32_t)d;
+      const uint32_t ci = (lo >> (2u * i)) & MASK;
+      if (((st >> i) & 1u) && (ci == code || (BOTH && ci == rc))) on = false;
+    }
+  }
+  const uint32_t c = pos_coordinate(anchor, p, D);  // (junk where p > D: no word stands there)
+  if (on && c >= c0 && c < c1) {
+    const uint32_t b = (c - c0) / S;
+    atomicAdd(&bins[(b << (2 * K)) + (rc < code ? rc : code)], 1u);
+  }
+}
+
+// the public key of a bin: the K digits of its code in reverse order (first base highest), folded on both strands
+template <int K, bool BOTH>
+__device__ __forceinline__ uint32_t pos_public_key(uint32_t code) {
+  const uint32_t key = revcomp32(~code, K);
+  if (!BOTH) return key;
+  const uint32_t rc = revcomp32(key, K);
+  return rc < key ? rc : key;
+}
+
+template <int K, bool BOTH>
+__device__ __forceinline__ void pos_flush(uint32_t* bins, int b0, int nb, unsigned long long* __restrict__ counts) {
+  constexpr int NK = 1 << (2 * K);
+  __syncthreads();
+  for (int q = threadIdx.x; q < nb * NK; q += POS_THREADS) {
+    const uint32_t c = bins[q];
+    if (c) {
+      bins[q] = 0u;
+      atomicAdd(&counts[(uint64_t)(b0 + q / NK) * NK + pos_public_key<K, BOTH>((uint32_t)q % NK)], (unsigned long long)c);
+    }
+  }
+  __syncthreads();
+}
+
+template <int K, bool BOTH>
+__global__ __launch_bounds__(POS_THREADS) void pos_count_kernel(const uint64_t* __restrict__ words, const uint32_t* __restrict__ valid,
+                                                                const int64_t* __restrict__ offs, const uint32_t* __restrict__ lens,
+                                                                uint64_t n_seq, int anchor, uint32_t S, int n_bins, int per_group,
+                                                                const unsigned long long* __restrict__ excl,
+                                                                const unsigned long long* __restrict__ boff, uint64_t n_groups,
+                                                                unsigned long long* __restrict__ counts) {
+  constexpr int NK = 1 << (2 * K);
+  extern __shared__ __attribute__((aligned(16))) uint32_t sh[];  // (b1 - b0) tables
+  const int b0 = (int)blockIdx.y * per_group, b1 = std::min(n_bins, b0 + per_group), nb = b1 - b0;
+  const uint32_t c0 = (uint32_t)b0 * S, c1 = (uint32_t)b1 * S, R = (uint32_t)n_bins * S;
+  // this wave's share of the tiles: [g, gend); `per` rounds for every wave of the grid
+  const uint64_t total = boff[n_groups];
+  const uint64_t n_waves = (uint64_t)gridDim.x * POS_WAVES;
+  const uint64_t per = (total + n_waves - 1) / n_waves;
+  if ((uint64_t)blockIdx.x * POS_WAVES * per >= total) return;  // (the whole workgroup: nothing to zero, nothing to flush)
+  for (int q = threadIdx.x; q < nb * NK; q += POS_THREADS) sh[q] = 0u;
+  __syncthreads();
+  const uint64_t wave = (uint64_t)blockIdx.x * POS_WAVES + (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  uint64_t g = wave * per;
+  const uint64_t gend = g + per < total ? g + per : total;
+  uint64_t i = 0;
+  uint32_t k = 0, L = 0;
+  PosTiles t = {0u, 0u};
+  if (g < gend) {
+    // the sequence and the tile of it that g is: the last group with boff <= g, the last sequence of it with excl <= rest
+    uint64_t lo = 0, hi = n_groups;  // boff[lo] <= g < boff[hi]
+    while (hi - lo > 1) {
+      const uint64_t mid = lo + (hi - lo) / 2;
+      if (boff[mid] <= g) lo = mid;
+      else hi = mid;
+    }
+    const uint64_t rest = g - boff[lo];
+    i = lo * POS_SCAN_THREADS;
+    uint64_t ihi = std::min<uint64_t>(n_seq, i + POS_SCAN_THREADS);
+    while (ihi - i > 1) {
+      const uint64_t mid = i + (ihi - i) / 2;
+      if (excl[mid] <= rest) i = mid;
+      else ihi = mid;
+    }
+    k = (uint32_t)(rest - excl[i]);
+    L = lens[i];
+    t = pos_tiles(L, K, anchor, R);
+  }
+  uint32_t since = 0;
+  for (uint64_t round = 0; round < per; ++round) {  // (per, and so every barrier below, is the same for the whole grid)
+    if (g < gend) {
+      while (k >= t.nt) {  // the next sequence that has a tile (there is one: g < total)
+        if (++i >= n_seq) break;
+        L = lens[i];
+        t = pos_tiles(L, K, anchor, R);
+        k = 0;
+      }
+      if (i < n_seq) {
+        const uint64_t w0 = (uint64_t)offs[i] >> 5;
+        pos_tile<K, BOTH>(words + w0, valid ? valid + w0 : nullptr, L, t.k0 + k, anchor, S, c0, c1, sh);
+      }
+      ++k;
+      ++g;
+    }
+    if (++since == POS_FLUSH_ROUNDS) {
+      pos_flush<K, BOTH>(sh, b0, nb, counts);
+      since = 0;
+    }
+  }
+  if (since) pos_flush<K, BOTH>(sh, b0, nb, counts);
+}
+
+template <int K, bool BOTH>
+int pos_launch(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_valid, const int64_t* d_offs, const uint32_t* d_lens,
+               uint64_t n_seq, int anchor, uint32_t S, int n_bins, const unsigned long long* excl, const unsigned long long* boff,
+               uint64_t n_groups, uint64_t* d_counts) {
+  // the bins in equal groups of at most pos_max_per_group(K): 20 bins at K = 6 are 3 x 7
+  const int bin_groups = (n_bins + pos_max_per_group(K) - 1) / pos_max_per_group(K);
+  const int per_group = (n_bins + bin_groups - 1) / bin_groups;
+  const size_t lds = ((size_t)per_group << (2 * K)) * sizeof(uint32_t);
+  const unsigned per_cu = lds * 2 <= 160 * 1024 ? 2u : 1u;  // (32 waves a CU: two workgroups of 1024 threads at most)
+  const dim3 grid((unsigned)ctx->num_cu * per_cu, (unsigned)bin_groups);
+  PENGK_HIP(hipFuncSetAttribute((const void*)pos_count_kernel<K, BOTH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL((pos_count_kernel<K, BOTH>), grid, dim3(POS_THREADS), lds, ctx->stream, d_words, d_valid, d_offs, d_lens, n_seq,
+                     anchor, S, n_bins, per_group, excl, boff, n_groups, (unsigned long long*)d_counts);
+  PENGK_HIP(hipGetLastError());
+  return PENGK_OK;
+}
+
+inline uint64_t pos_keys(int K, int both) {
+  const uint64_t all = 1ull << (2 * K);
+  if (!both) return all;
+  return (K & 1) ? all / 2 : (all + (1ull << K)) / 2;
+}
+
+}  // namespace
+}  // namespace pengk
+
+using namespace pengk;
+
+extern "C" {
+
+int pengk_position_count(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_valid, const int64_t* d_offs, const uint32_t* d_lens,
+                         uint64_t n_seq, int K, int anchor, int bin_size, int n_bins, int both_strands, uint64_t* d_counts) {
+  if (!ctx || (n_seq && (!d_words || !d_offs || !d_lens || !d_counts))) return fail(PENGK_ERR_ARG, "pengk_position_count: bad argument");
+  if (K < PENGK_POSITION_MIN_K || K > PENGK_POSITION_MAX_K)
+    return fail(PENGK_ERR_ARG, "pengk_position_count: K %d out of range [%d,%d]", K, PENGK_POSITION_MIN_K, PENGK_POSITION_MAX_K);
+  if (anchor < 0 || anchor > 2) return fail(PENGK_ERR_ARG, "pengk_position_count: anchor must be 0 (start), 1 (end) or 2 (centre)");
+  if (bin_size < 1 || bin_size > PENGK_POSITION_MAX_BIN_SIZE)
+    return fail(PENGK_ERR_ARG, "pengk_position_count: bin_size %d out of range [1,%d]", bin_size, PENGK_POSITION_MAX_BIN_SIZE);
+  if (n_bins < 1 || n_bins > PENGK_POSITION_MAX_BINS)
+    return fail(PENGK_ERR_ARG, "pengk_position_count: n_bins %d out of range [1,%d]", n_bins, PENGK_POSITION_MAX_BINS);
+  if (both_strands != 0 && both_strands != 1) return fail(PENGK_ERR_ARG, "pengk_position_count: both_strands must be 0 or 1");
+  if (n_seq >> 32) return fail(PENGK_ERR_ARG, "pengk_position_count: 2^32 sequences or more; shard the input");
+  int rc = enter(ctx);
+  if (rc) return rc;
+  if (n_seq == 0) return PENGK_OK;
+  const uint64_t n_groups = (n_seq + POS_SCAN_THREADS - 1) / POS_SCAN_THREADS;
+  // scratch: excl (n_seq uint64) | boff (n_groups + 1 uint64)
+  rc = ensure_scratch(ctx, &ctx->d_sites, &ctx->sites_bytes, (n_seq + n_groups + 1) * sizeof(uint64_t));
+  if (rc) return rc;
+  unsigned long long* excl = (unsigned long long*)ctx->d_sites;
+  unsigned long long* boff = excl + n_seq;
+  hipLaunchKernelGGL(pos_tiles_kernel, dim3((unsigned)n_groups), dim3(POS_SCAN_THREADS), 0, ctx->stream, d_lens, n_seq, K, anchor,
+                     (uint32_t)bin_size * (uint32_t)n_bins, excl, boff);
+  hipLaunchKernelGGL(pos_groups_kernel, dim3(1), dim3(POS_SCAN_THREADS), 0, ctx->stream, boff, n_groups);
+#define PENGK_POS_CASE(k)                                                                                                          \
+  case k:                                                                                                                          \
+    return both_strands ? pos_launch<k, true>(ctx, d_words, d_valid, d_offs, d_lens, n_seq, anchor, (uint32_t)bin_size, n_bins, excl,  \
+                                              boff, n_groups, d_counts)                                                            \
+                        : pos_launch<k, false>(ctx, d_words, d_valid, d_offs, d_lens, n_seq, anchor, (uint32_t)bin_size, n_bins, excl, \
+                                               boff, n_groups, d_counts)
+  switch (K) {
+    PENGK_POS_CASE(4);
+    PENGK_POS_CASE(5);
+    PENGK_POS_CASE(6);
+    PENGK_POS_CASE(7);
+  }
+#undef PENGK_POS_CASE
+  return PENGK_OK;
+}
+
+int pengk_position_summary(const uint64_t* h_counts, int K, int n_bins, int both_strands, uint64_t min_count, double max_evalue,
+                           pengk_position_word* out, uint64_t capacity, uint64_t* n_out) {
+  if (!h_counts || !n_out || (capacity && !out)) return fail(PENGK_ERR_ARG, "pengk_position_summary: bad argument");
+  if (K < PENGK_POSITION_MIN_K || K > PENGK_POSITION_MAX_K)
+    return fail(PENGK_ERR_ARG, "pengk_position_summary: K %d out of range [%d,%d]", K, PENGK_POSITION_MIN_K, PENGK_POSITION_MAX_K);
+  if (n_bins < 1 || n_bins > PENGK_POSITION_MAX_BINS)
+    return fail(PENGK_ERR_ARG, "pengk_position_summary: n_bins %d out of range [1,%d]", n_bins, PENGK_POSITION_MAX_BINS);
+  if (both_strands != 0 && both_strands != 1) return fail(PENGK_ERR_ARG, "pengk_position_summary: both_strands must be 0 or 1");
+  if (!(max_evalue > 0.0)) return fail(PENGK_ERR_ARG, "pengk_position_summary: max_evalue must be positive");
+  *n_out = 0;
+  const uint32_t NK = 1u << (2 * K);
+  std::vector<uint64_t> N((size_t)n_bins, 0), C(NK, 0);
+  uint64_t Nt = 0;
+  for (int b = 0; b < n_bins; ++b)
+    for (uint32_t key = 0; key < NK; ++key) {
+      const uint64_t c = h_counts[(size_t)b * NK + key];
+      N[b] += c;
+      C[key] += c;
+    }
+  for (int b = 0; b < n_bins; ++b) Nt += N[b];
+  if (Nt == 0) return PENGK_OK;
+  std::vector<double> q((size_t)n_bins);
+  for (int b = 0; b < n_bins; ++b) q[b] = (double)N[b] / (double)Nt;
+  const double log_tests = std::log10((double)((uint64_t)n_bins * pos_keys(K, both_strands)));
+  const double log_max = std::log10(max_evalue);
+  std::vector<pengk_position_word> rep;
+  for (uint32_t key = 0; key < NK; ++key) {
+    if (C[key] == 0) continue;
+    pengk_position_word best = {};
+    bool have = false;
+    uint32_t significant = 0;
+    for (int b = 0; b < n_bins; ++b) {
+      const uint64_t c = h_counts[(size_t)b * NK + key];
+      if (c == 0 || c < min_count) continue;
+      const double expected = (double)C[key] * q[b];
+      if (!((double)c > expected)) continue;
+      pengk_position_word w;
+      w.key = key;
+      w.bin = (uint32_t)b;
+      w.count = c;
+      w.total = C[key];
+      w.bin_positions = N[b];
+      w.expected = expected;
+      const int rc = pengk_binomial_log10_sf(C[key], c, q[b], &w.log10_pvalue);
+      if (rc) return rc;
+      w.log10_evalue = w.log10_pvalue + log_tests;
+      if (w.log10_evalue <= log_max) ++significant;
+      if (!have || w.log10_evalue < best.log10_evalue) {
+        best = w;
+        have = true;
+      }
+    }
+    if (!have || !(best.log10_evalue <= log_max)) continue;
+    best.bins_significant = significant;
+    best.family = 0;
+    best.is_head = 0;
+    rep.push_back(best);
+  }
+  std::sort(rep.begin(), rep.end(), [](const pengk_position_word& x, const pengk_position_word& y) {
+    if (x.log10_evalue != y.log10_evalue) return x.log10_evalue < y.log10_evalue;
+    if (x.bin != y.bin) return x.bin < y.bin;
+    return x.key < y.key;
+  });
+  // families: the word as letters 0 .. 3; the heads so far, each tried at the offsets -2 .. 2
+  auto letters = [K](uint32_t key, bool rc, uint8_t* s) {
+    if (rc) key = revcomp32(key, K);
+    for (int c = 0; c < K; ++c) s[c] = (uint8_t)((key >> (2 * (K - 1 - c))) & 3u);
+  };
+  auto related = [K](const uint8_t* X, const uint8_t* Y) {
+    for (int o = -2; o <= 2; ++o) {
+      int same = 0;
+      bool clash = false;
+      for (int c = 0; c < K; ++c) {
+        const int cy = c - o;
+        if (cy < 0 || cy >= K) continue;
+        if (X[c] == Y[cy]) ++same;
+        else clash = true;
+      }
+      if (!clash && same >= 4) return true;
+    }
+    return false;
+  };
+  std::vector<uint32_t> heads;  // indices into rep
+  for (size_t k = 0; k < rep.size(); ++k) {
+    uint8_t Y[2][8], X[8];
+    letters(rep[k].key, false, Y[0]);
+    if (both_strands) letters(rep[k].key, true, Y[1]);
+    uint32_t fam = 0;
+    for (uint32_t h : heads) {
+      const uint32_t far = rep[h].bin > rep[k].bin ? rep[h].bin - rep[k].bin : rep[k].bin - rep[h].bin;
+      if (far > 1u) continue;
+      letters(rep[h].key, false, X);
+      if (related(X, Y[0]) || (both_strands && related(X, Y[1]))) {
+        fam = h + 1u;
+        break;
+      }
+    }
+    if (!fam) {
+      heads.push_back((uint32_t)k);
+      fam = (uint32_t)k + 1u;
+      rep[k].is_head = 1;
+    }
+    rep[k].family = fam;
+  }
+  *n_out = rep.size();
+  for (size_t k = 0; k < rep.size() && k < capacity; ++k) out[k] = rep[k];
+  return PENGK_OK;
+}
+
+}  // extern "C"

@@ -94,6 +94,13 @@ unsigned long long Global::dyadsMinCount = 5;
 char* Global::dyadsMotifsFilename = nullptr;
 int Global::dyadsTop = 5;
 double Global::dyadsPvalue = 1e-3;  // (an exact six-letter match has p = 4^-6 = 2.4e-4: --refine's 1e-4 would find no site)
+char* Global::positionalFilename = nullptr;
+int Global::positionalWidth = 6;
+int Global::positionalAnchor = 2;  // center
+int Global::positionalBinSize = 10;
+int Global::positionalBins = 20;
+double Global::positionalEvalue = 0.01;
+unsigned long long Global::positionalMinCount = 5;
 bool Global::discriminative = false;
 double Global::discriminativePseudocount = 1.0;
 bool Global::scoreNegativesControl = false;
@@ -118,7 +125,7 @@ void Global::init(int nargs, char* args[]) {
   // enrichment scan the input after the motifs are found)
   pengk_host::keep_host_codes(scoreMotifs || sitesFilename || centralityFilename || refineFilename || spacingFilename ||
                               dinucFilename || enrichFilename || eraseFilename || maskLowComplexity || holdoutFilename ||
-                              dyadsFilename);
+                              dyadsFilename || positionalFilename);
   // both strands are handled inside the count; sequences are always read single stranded
   // ... and every chunk of the input set is packed and sent to the device while the rest is still being read
   pengk_host::begin_streaming_pack(patternLength);
@@ -208,6 +215,7 @@ void Global::readArguments(int nargs, char* args[]) {
   const char* holdout_option = nullptr;  // the last option given that only means something with --holdout
   const char* mask_option = nullptr;  // the last option given that only means something with --mask-low-complexity
   const char* dyads_option = nullptr;  // ... with --dyads
+  const char* positional_option = nullptr;  // ... with --positional
   for (int i = 2; i < nargs; i++) {
     const char* a = args[i];
     if (!strcmp(a, "-w")) {
@@ -567,6 +575,53 @@ void Global::readArguments(int nargs, char* args[]) {
       }
       (ev ? dyadsEvalue : dyadsPvalue) = x;
       dyads_option = ev ? "--dyads-evalue" : "--dyads-pvalue";
+    } else if (!strcmp(a, "--positional")) {
+      positionalFilename = (char*)need(i, nargs, args, printHelp);
+    } else if (!strcmp(a, "--positional-anchor")) {
+      const char* v = need(i, nargs, args, printHelp);
+      if (!strcmp(v, "start")) positionalAnchor = 0;
+      else if (!strcmp(v, "end")) positionalAnchor = 1;
+      else if (!strcmp(v, "center")) positionalAnchor = 2;
+      else {
+        printHelp();
+        log_line("ERROR", "--positional-anchor must be start, end or center");
+        exit(4);
+      }
+      positional_option = "--positional-anchor";
+    } else if (!strcmp(a, "--positional-width") || !strcmp(a, "--positional-bin-size") || !strcmp(a, "--positional-bins") ||
+               !strcmp(a, "--positional-min-count")) {
+      const int which = !strcmp(a, "--positional-width") ? 0 : !strcmp(a, "--positional-bin-size") ? 1 : !strcmp(a, "--positional-bins") ? 2 : 3;
+      static const char* const kName[4] = {"--positional-width", "--positional-bin-size", "--positional-bins", "--positional-min-count"};
+      static const char* const kRange[4] = {"--positional-width must be an integer in [4, 7]",
+                                            "--positional-bin-size must be an integer in [1, 65536]",
+                                            "--positional-bins must be an integer in [1, 64]",
+                                            "--positional-min-count must be an integer in [1, 1000000000]"};
+      static const long long kLo[4] = {PENGK_POSITION_MIN_K, 1, 1, 1};
+      static const long long kHi[4] = {PENGK_POSITION_MAX_K, PENGK_POSITION_MAX_BIN_SIZE, PENGK_POSITION_MAX_BINS, 1000000000ll};
+      const char* v = need(i, nargs, args, printHelp);
+      char* end = nullptr;
+      const long long n = std::strtoll(v, &end, 10);
+      if (end == v || *end || n < kLo[which] || n > kHi[which]) {
+        printHelp();
+        log_line("ERROR", kRange[which]);
+        exit(4);
+      }
+      if (which == 0) positionalWidth = (int)n;
+      else if (which == 1) positionalBinSize = (int)n;
+      else if (which == 2) positionalBins = (int)n;
+      else positionalMinCount = (unsigned long long)n;
+      positional_option = kName[which];
+    } else if (!strcmp(a, "--positional-evalue")) {
+      const char* v = need(i, nargs, args, printHelp);
+      char* end = nullptr;
+      const double x = std::strtod(v, &end);
+      if (end == v || *end || !(x > 0.0) || !(x <= 1e300)) {
+        printHelp();
+        log_line("ERROR", "--positional-evalue must be a positive number");
+        exit(4);
+      }
+      positionalEvalue = x;
+      positional_option = "--positional-evalue";
     } else if (!strcmp(a, "--discriminative")) {
       discriminative = true;
     } else if (!strcmp(a, "--discriminative-pseudocount")) {
@@ -630,6 +685,11 @@ void Global::readArguments(int nargs, char* args[]) {
   if (dyads_option && !dyadsFilename) {
     printHelp();
     log_line("ERROR", std::string(dyads_option) + " requires --dyads");
+    exit(4);
+  }
+  if (positional_option && !positionalFilename) {
+    printHelp();
+    log_line("ERROR", std::string(positional_option) + " requires --positional");
     exit(4);
   }
   if (mask_option && !maskLowComplexity) {
@@ -701,6 +761,19 @@ void Global::printHelp() {
   printf("  --dyads-motifs FILE            the first family heads refined from their sites as --refine does it, as MEME\n");
   printf("  --dyads-top INT                family heads refined, 1..64 (default 5)\n");
   printf("  --dyads-pvalue FLOAT           p-value threshold of a site in that refinement, in (0, 1] (default 1e-3)\n");
+  printf("  --positional FILE              count the words of --positional-width letters per position bin over what round 1\n");
+  printf("                                 counts (overlapping repeats of a word once), test each word's count in a bin against\n");
+  printf("                                 its count everywhere and the bin's share of all words (binomial, E-value over all\n");
+  printf("                                 words and bins) and fold shifted neighbours into families: words that keep one\n");
+  printf("                                 position (a TATA box, a splice signal) whether or not they are over-represented.\n");
+  printf("                                 FILE: one line per word, tab-separated\n");
+  printf("  --positional-width INT         letters of a word, 4..7 (default 6)\n");
+  printf("  --positional-anchor NAME       positions are measured from the start, the end or the center of a sequence\n");
+  printf("                                 (center: the unsigned distance; default center)\n");
+  printf("  --positional-bin-size INT      positions a bin holds, 1..65536 (default 10)\n");
+  printf("  --positional-bins INT          bins counted from the anchor on, 1..64 (default 20); words further out are ignored\n");
+  printf("  --positional-evalue FLOAT      a word is reported at this E-value or below (default 0.01)\n");
+  printf("  --positional-min-count INT     occurrences a word needs in its bin (default 5)\n");
   printf("  --erase FILE                   after the search, mask the sites of the motifs found and search what is left\n");
   printf("                                 again; the later rounds' motifs are appended.  FILE: one line per round and motif\n");
   printf("  --erase-rounds INT             further rounds of --erase, 1..8 (default 1); a round that finds or erases\n");

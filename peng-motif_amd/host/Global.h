@@ -110,6 +110,13 @@ class Global {
   static char* dyadsMotifsFilename;          // --dyads-motifs: the refined family heads as MEME
   static int dyadsTop;                       // --dyads-top: family heads refined
   static double dyadsPvalue;                 // --dyads-pvalue: site threshold of that refinement
+  static char* positionalFilename;           // --positional (new: words with a position bias counted on the device)
+  static int positionalWidth;                // --positional-width: PENGK_POSITION_MIN_K..PENGK_POSITION_MAX_K
+  static int positionalAnchor;               // --positional-anchor: 0 start, 1 end, 2 center
+  static int positionalBinSize;              // --positional-bin-size
+  static int positionalBins;                 // --positional-bins: 1..PENGK_POSITION_MAX_BINS
+  static double positionalEvalue;            // --positional-evalue
+  static unsigned long long positionalMinCount;  // --positional-min-count
   static bool discriminative;                // --discriminative (new: the k-mer sweep held to the control set's counts)
   static double discriminativePseudocount;   // --discriminative-pseudocount
   static bool scoreNegativesControl;         // --score-negatives control (new: the --background-sequences file as negatives, matched to the input)

@@ -23,6 +23,7 @@
 #include "motif_erase.h"
 #include "motif_holdout.h"
 #include "motif_match.h"
+#include "motif_positional.h"
 #include "motif_refine.h"
 #include "motif_spacing.h"
 #include "motif_sites.h"
@@ -143,6 +144,23 @@ int main(int nargs, char** args) {
     write_dyads(*Global::inputSequenceSet, *scan, lc_mask.erase_valid(), holdout.attached ? &training : nullptr, *bgModel,
                 Global::strand == Strand::BOTH_STRANDS, ds, rs, Global::dyadsFilename, Global::dyadsMotifsFilename);
     clock.lap("dyads");
+  }
+  // --positional: words with a position bias, over the same share behind the same mask
+  if (Global::positionalFilename && Global::patternLength >= PENGK_MIN_W && Global::patternLength <= PENGK_MAX_W) {
+    if (!scan) {
+      scan.reset(new ScanInput);
+      build_scan_input(*Global::inputSequenceSet, scan.get());
+    }
+    PositionalSettings ps;
+    ps.width = Global::positionalWidth;
+    ps.anchor = Global::positionalAnchor;
+    ps.bin_size = Global::positionalBinSize;
+    ps.bins = Global::positionalBins;
+    ps.evalue = Global::positionalEvalue;
+    ps.min_count = Global::positionalMinCount;
+    write_positional(*scan, lc_mask.erase_valid(), holdout.attached ? &training : nullptr, Global::strand == Strand::BOTH_STRANDS, ps,
+                     Global::positionalFilename);
+    clock.lap("positional");
   }
   Peng peng(Global::strand, Global::bgModelOrder, Global::maxOptBgModelOrder, Global::inputSequenceSet, bgModel);
 
