@@ -233,6 +233,48 @@ int pengk_pattern_stats_control(pengk_ctx* ctx, int W, int both_strands, int k, 
                                 const uint64_t* d_ctrl_ltot, double pseudocount, float* d_bgprob, float* d_expected,
                                 float* d_logp, float* d_z);
 
+/* ---- a GC-stratified null for the sweep (--stratified-background: on an input of mixed composition -- CpG-island
+ *      promoters pooled with A+T-rich enhancers -- every G+C-rich and every A+T-rich word is over-represented against ONE
+ *      Markov model; HOMER normalises for GC for the same reason) ---------------------
+ * This project's own definitions, not promised to give HOMER's numbers.  Integer counters and one fp64 mixture with one
+ * rounding: a numpy restatement and any sharding give the same bits.
+ *
+ * The background counters of every stratum of a scan layout (the layout of pengk_motif_scan; the strata of
+ * pengk_seq_strata with use_length = 0, or any other labelling below n_strata).  For every sequence i with
+ * d_stratum[i] = s < n_strata (any other value, 0xFFFF included, is skipped), every position p and every order k in
+ * 0 .. 2 with p >= k: the (k+1)-mer ending at p is counted, d_bg[s * 84 + at_k + y] += 1, iff ALL of its k + 1 bases are
+ * valid -- this project's own rule for invalid bases: an invalid base takes part in no word of any order, and the base
+ * behind it starts over at order 0 (the packer's bg_counts keep the reference's treatment of such bases; on an input
+ * without invalid bases the strata's counters sum to them exactly).  y: the word in BaMM order, older base more
+ * significant; at_k = 0 / 4 / 20.  d_valid = NULL: every base valid.  d_windows[s] (may be NULL) += the positions p with W
+ * consecutive valid bases from p on: the windows a count at pattern length W can see, the stratum's weight in
+ * pengk_pattern_stats_strata.  d_bg (n_strata x 84 uint64) and d_windows (n_strata uint64) are ADDED to (caller-zeroed):
+ * shards and several calls sum exactly.  n_seq = 0 does nothing.  PENGK_ERR_ARG: n_strata outside 1 .. 16, W not an even
+ * number in PENGK_MIN_W .. PENGK_MAX_W, n_seq >= 2^32, a null pointer (but d_valid and d_windows) with n_seq > 0.
+ * Asynchronous on the context's stream. */
+int pengk_strata_bg_count(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_valid /* NULL: all valid */,
+                          const int64_t* d_offs, const uint32_t* d_lens, uint64_t n_seq, const uint16_t* d_stratum,
+                          int n_strata /* 1..16 */, int W, uint64_t* d_bg /* n_strata x 84, ADDED to */,
+                          uint64_t* d_windows /* n_strata, ADDED to; may be NULL */);
+/* The sweep under the mixture of the strata's models.  d_V: float[n_strata][84], a V table (pengk_bg_model) per stratum;
+ * h_windows: n_strata HOST uint64 weights w_s (read before the call returns).  With p_{s,o}[x] the strand-aggregated
+ * float32 probability that pengk_pattern_stats would write to bgprob[o][x] for the table V_s, for every order o <= max_k
+ *     m_o[x] = (float)( (sum over s of (double) w_s * (double) p_{s,o}[x]) / (double)(sum over s of w_s) )
+ * -- the sum in fp64 in ascending s over the strata with w_s > 0, product and addition rounded separately, the weights'
+ * sum in uint64, ONE division and ONE rounding to float32.  One non-zero weight gives pengk_pattern_stats' bits for that
+ * stratum's table.  With a control (d_ctrl_counts, d_ctrl_ltot, pseudocount as pengk_pattern_stats_control takes them;
+ * NULL, NULL, 0: none) q_o[x] = (float) fmax((double) m_o[x], share[x]) with that entry's share.  d_bgprob receives m_o
+ * (q_o); expected, log-p and z are made of m_k (q_k), d_ltot and d_counts exactly as pengk_pattern_stats makes them of
+ * p_k.  Every even W from 2 to 14; the result does not depend on the option sweep_pairs.  PENGK_ERR_ARG: a NULL argument
+ * (but the control's), n_strata outside 1 .. 16, every weight zero or their sum beyond 2^64, one control pointer without
+ * the other, a pseudocount that is not finite and >= 0, or not 0 without a control.  Asynchronous on the context's
+ * stream: no host wait. */
+int pengk_pattern_stats_strata(pengk_ctx* ctx, int W, int both_strands, int k, int max_k, const float* d_V /* n_strata x 84 */,
+                               int n_strata, const uint64_t* h_windows /* n_strata */, const uint64_t* d_ltot,
+                               const uint32_t* d_counts, const uint32_t* d_ctrl_counts, const uint64_t* d_ctrl_ltot,
+                               double pseudocount /* control: NULL, NULL, 0 = none */, float* d_bgprob, float* d_expected,
+                               float* d_logp, float* d_z);
+
 /* ---- seed candidates (first half of BasePattern::select_base_patterns, src/base_pattern.cpp:443-515) ----------------
  * The reference std::sorts all 4^W ids by z-score and walks the ranking down to the threshold (:458-466); only ids with
  * z >= z_threshold and count >= count_threshold can become seeds.  This call compacts exactly those on the device

@@ -26,6 +26,7 @@ EXPORTS = [
     "pengk_memset", "pengk_warmup", "pengk_host_alloc", "pengk_host_free", "pengk_timer_create", "pengk_timer_record", "pengk_timer_elapsed_ms", "pengk_timer_destroy",
     "pengk_pack", "pengk_pack_threads", "pengk_pack_append", "pengk_packed_free", "pengk_set_sequences", "pengk_synth_sizes", "pengk_synth_sequences",
     "pengk_count", "pengk_count_bg", "pengk_mirror_counts", "pengk_bg_count", "pengk_bg_model", "pengk_pattern_stats", "pengk_pattern_stats_control",
+    "pengk_strata_bg_count", "pengk_pattern_stats_strata",
     "pengk_seed_candidates", "pengk_iupac_aggregate", "pengk_em", "pengk_em_device", "pengk_test_em_generation", "pengk_sequential_sum_f32", "pengk_motif_similarity", "pengk_selftest_division",
     "pengk_comm_unique_id", "pengk_comm_init", "pengk_comm_init_env", "pengk_comm_info", "pengk_comm_init_abandoned", "pengk_comm_rccl_version", "pengk_comm_destroy",
     "pengk_allreduce_tables", "pengk_comm_check_bin_bound", "pengk_allgather",
@@ -162,6 +163,8 @@ def lib():
         L.pengk_bg_model.argtypes = [vp, vp, C.c_int, vp, vp]
         L.pengk_pattern_stats.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]
         L.pengk_pattern_stats_control.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_double, vp, vp, vp, vp]
+        L.pengk_strata_bg_count.argtypes = [vp, vp, vp, vp, vp, u64, vp, C.c_int, C.c_int, vp, vp]
+        L.pengk_pattern_stats_strata.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, C.c_double, vp, vp, vp, vp]
         L.pengk_seed_candidates.argtypes = [vp, C.c_int, vp, vp, f32, u64, vp, vp, i64, C.POINTER(i64)]
         L.pengk_iupac_aggregate.argtypes = [vp, C.c_int, C.c_int, vp, i64, vp, vp, vp, vp]
         L.pengk_em.argtypes = [vp, C.c_int, i64, vp, f32, f32, C.c_int, vp, vp, vp, vp]
@@ -734,6 +737,39 @@ class Context:
         _check(lib().pengk_pattern_stats_control(self.h, W, int(both), k, max_k, _ptr(V), _ptr(ltot), _ptr(counts), _ptr(ctrl_counts),
                                                  _ptr(ctrl_ltot), float(pseudocount), _ptr(bgprob), _ptr(expected), _ptr(logp), _ptr(z)))
         return bgprob, expected, logp, z
+
+    def pattern_stats_strata(self, W, both, k, max_k, V, windows, ltot, counts, ctrl_counts=None, ctrl_ltot=None, pseudocount=0.0,
+                             bgprob=None, expected=None, logp=None, z=None, n_strata=None):
+        """the sweep under the mixture of the strata's models (pengk_pattern_stats_strata).  V: device float32
+        [n_strata x 84]; windows: the n_strata host weights; ctrl_counts / ctrl_ltot / pseudocount: the control of
+        pattern_stats_control, or none.  n_strata: another count than len(windows) (argument tests)."""
+        w = np.ascontiguousarray(windows, np.uint64)
+        n = 4 ** W
+        bgprob = bgprob if bgprob is not None else self.empty((max_k + 1, n), np.float32)
+        expected = expected if expected is not None else self.empty(n, np.float32)
+        logp = logp if logp is not None else self.empty(n, np.float32)
+        z = z if z is not None else self.empty(n, np.float32)
+        _check(lib().pengk_pattern_stats_strata(self.h, W, int(both), k, max_k, _ptr(V), len(w) if n_strata is None else n_strata,
+                                                w.ctypes.data, _ptr(ltot), _ptr(counts),
+                                                None if ctrl_counts is None else _ptr(ctrl_counts),
+                                                None if ctrl_ltot is None else _ptr(ctrl_ltot), float(pseudocount), _ptr(bgprob),
+                                                _ptr(expected), _ptr(logp), _ptr(z)))
+        return bgprob, expected, logp, z
+
+    def strata_bg_count(self, scan, stratum, n_strata, W, all_valid=False, bg=None, windows=None, n_seq=None, want_windows=True):
+        """(bg, windows), both on the device: the n_strata x 84 background counters and the n_strata window counts of `scan`
+        under the strata `stratum` (device uint16 per sequence; pengk_strata_bg_count).  all_valid: d_valid = NULL.  bg /
+        windows: device uint64 arrays to ADD to instead of fresh zeroed ones.  want_windows = False: d_windows = NULL.
+        n_seq: another count than scan[4] (argument tests)."""
+        rows = max(1, min(int(n_strata), 16))
+        if bg is None:
+            bg = self.to_device(np.zeros((rows, 84), np.uint64))
+        if windows is None and want_windows:
+            windows = self.to_device(np.zeros(rows, np.uint64))
+        _check(lib().pengk_strata_bg_count(self.h, _ptr(scan[0]), None if all_valid else _ptr(scan[1]), _ptr(scan[2]), _ptr(scan[3]),
+                                           scan[4] if n_seq is None else n_seq, _ptr(stratum), int(n_strata), int(W), _ptr(bg),
+                                           _ptr(windows) if want_windows else None))
+        return bg, windows
 
     def iupac_aggregate(self, W, both, ids, counts, bgp, expected):
         ids = np.ascontiguousarray(ids, np.uint64)

@@ -101,6 +101,10 @@ int Global::positionalBinSize = 10;
 int Global::positionalBins = 20;
 double Global::positionalEvalue = 0.01;
 unsigned long long Global::positionalMinCount = 5;
+bool Global::stratifiedBackground = false;
+int Global::stratifiedGcBins = 10;
+unsigned long long Global::stratifiedMinBases = 10000;
+char* Global::stratifiedReportFilename = nullptr;
 bool Global::discriminative = false;
 double Global::discriminativePseudocount = 1.0;
 bool Global::scoreNegativesControl = false;
@@ -125,7 +129,7 @@ void Global::init(int nargs, char* args[]) {
   // enrichment scan the input after the motifs are found)
   pengk_host::keep_host_codes(scoreMotifs || sitesFilename || centralityFilename || refineFilename || spacingFilename ||
                               dinucFilename || enrichFilename || eraseFilename || maskLowComplexity || holdoutFilename ||
-                              dyadsFilename || positionalFilename);
+                              dyadsFilename || positionalFilename || stratifiedBackground);
   // both strands are handled inside the count; sequences are always read single stranded
   // ... and every chunk of the input set is packed and sent to the device while the rest is still being read
   pengk_host::begin_streaming_pack(patternLength);
@@ -216,6 +220,7 @@ void Global::readArguments(int nargs, char* args[]) {
   const char* mask_option = nullptr;  // the last option given that only means something with --mask-low-complexity
   const char* dyads_option = nullptr;  // ... with --dyads
   const char* positional_option = nullptr;  // ... with --positional
+  const char* stratified_option = nullptr;  // ... with --stratified-background
   for (int i = 2; i < nargs; i++) {
     const char* a = args[i];
     if (!strcmp(a, "-w")) {
@@ -622,6 +627,25 @@ void Global::readArguments(int nargs, char* args[]) {
       }
       positionalEvalue = x;
       positional_option = "--positional-evalue";
+    } else if (!strcmp(a, "--stratified-background")) {
+      stratifiedBackground = true;
+    } else if (!strcmp(a, "--stratified-report")) {
+      stratifiedReportFilename = (char*)need(i, nargs, args, printHelp);
+      stratified_option = "--stratified-report";
+    } else if (!strcmp(a, "--stratified-gc-bins") || !strcmp(a, "--stratified-min-bases")) {
+      const bool bins = !strcmp(a, "--stratified-gc-bins");
+      const char* v = need(i, nargs, args, printHelp);
+      char* end = nullptr;
+      const long long n = std::strtoll(v, &end, 10);
+      if (end == v || *end || n < (bins ? 1 : 0) || n > (bins ? 16 : 1000000000000ll)) {
+        printHelp();
+        log_line("ERROR", bins ? "--stratified-gc-bins must be an integer in [1, 16]"
+                               : "--stratified-min-bases must be an integer in [0, 1000000000000]");
+        exit(4);
+      }
+      if (bins) stratifiedGcBins = (int)n;
+      else stratifiedMinBases = (unsigned long long)n;
+      stratified_option = bins ? "--stratified-gc-bins" : "--stratified-min-bases";
     } else if (!strcmp(a, "--discriminative")) {
       discriminative = true;
     } else if (!strcmp(a, "--discriminative-pseudocount")) {
@@ -685,6 +709,11 @@ void Global::readArguments(int nargs, char* args[]) {
   if (dyads_option && !dyadsFilename) {
     printHelp();
     log_line("ERROR", std::string(dyads_option) + " requires --dyads");
+    exit(4);
+  }
+  if (stratified_option && !stratifiedBackground) {
+    printHelp();
+    log_line("ERROR", std::string(stratified_option) + " requires --stratified-background");
     exit(4);
   }
   if (positional_option && !positionalFilename) {
@@ -774,6 +803,16 @@ void Global::printHelp() {
   printf("  --positional-bins INT          bins counted from the anchor on, 1..64 (default 20); words further out are ignored\n");
   printf("  --positional-evalue FLOAT      a word is reported at this E-value or below (default 0.01)\n");
   printf("  --positional-min-count INT     occurrences a word needs in its bin (default 5)\n");
+  printf("  --stratified-background        score the k-mers against a GC-stratified null: the sequences are put into GC bins, every\n");
+  printf("                                 bin gets a background model of its own (same order, alpha and interpolation) from the\n");
+  printf("                                 background set's sequences of that bin, and a k-mer's probability is the mean of the\n");
+  printf("                                 bins' Markov probabilities weighted by the windows the counted input holds in each.\n");
+  printf("                                 For inputs of mixed composition, where G+C-rich and A+T-rich words are enriched\n");
+  printf("                                 against one model.  The reports' log-odds and p-values keep the one model\n");
+  printf("  --stratified-gc-bins INT       GC bins, 1..16 (default 10)\n");
+  printf("  --stratified-min-bases INT     a bin whose model would be trained on fewer bases takes the global model (default 10000)\n");
+  printf("  --stratified-report FILE       one line per bin, tab-separated: its GC range, sequences, windows, model bases,\n");
+  printf("                                 the model used (own | global) and its four base probabilities\n");
   printf("  --erase FILE                   after the search, mask the sites of the motifs found and search what is left\n");
   printf("                                 again; the later rounds' motifs are appended.  FILE: one line per round and motif\n");
   printf("  --erase-rounds INT             further rounds of --erase, 1..8 (default 1); a round that finds or erases\n");

@@ -117,6 +117,10 @@ class Global {
   static int positionalBins;                 // --positional-bins: 1..PENGK_POSITION_MAX_BINS
   static double positionalEvalue;            // --positional-evalue
   static unsigned long long positionalMinCount;  // --positional-min-count
+  static bool stratifiedBackground;          // --stratified-background (new: a GC-stratified null for the k-mer sweep)
+  static int stratifiedGcBins;               // --stratified-gc-bins: 1..16
+  static unsigned long long stratifiedMinBases;  // --stratified-min-bases: a stratum with fewer model bases takes the global model
+  static char* stratifiedReportFilename;     // --stratified-report
   static bool discriminative;                // --discriminative (new: the k-mer sweep held to the control set's counts)
   static double discriminativePseudocount;   // --discriminative-pseudocount
   static bool scoreNegativesControl;         // --score-negatives control (new: the --background-sequences file as negatives, matched to the input)

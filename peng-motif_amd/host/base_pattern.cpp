@@ -15,6 +15,7 @@
 #include <iostream>
 
 #include "Global.h"
+#include "motif_strata.h"
 #include "ranked_prefix.h"
 #include "utils.h"
 
@@ -128,7 +129,20 @@ BasePattern::BasePattern(const size_t pattern_length, Strand s, const int k, con
   d_V.upload(hV, 84);
   d_bgprob.resize((size_t)(this->max_k + 1) * NP);
   d_expected.resize(NP);
-  if (discriminative)
+  // --stratified-background: the mixture of the GC strata's models in place of the one model, the control's share on top
+  // of it under --discriminative; d_V still holds the one model, which the dump below leaves as V.f32
+  const StratifiedNull* strata = pengk_host::stratified_null();
+  if (strata) {
+    pengk_host::DeviceBuffer<float> d_strata_V(strata->V.size());
+    d_strata_V.upload(strata->V.data(), strata->V.size());
+    check(pengk_pattern_stats_strata(context(), W, both, this->k, this->max_k, d_strata_V.get(), strata->G, strata->windows.data(),
+                                     d_ltot.get(), d_counts.get(), discriminative ? d_ctrl_counts.get() : nullptr,
+                                     discriminative ? d_ctrl_ltot.get() : nullptr,
+                                     discriminative ? Global::discriminativePseudocount : 0.0, d_bgprob.get(), d_expected.get(),
+                                     d_logp.get(), d_z.get()),
+          "pengk_pattern_stats_strata");
+    check(pengk_synchronize(context()), "pengk_synchronize");  // (the strata's tables leave scope here)
+  } else if (discriminative)
     check(pengk_pattern_stats_control(context(), W, both, this->k, this->max_k, d_V.get(), d_ltot.get(), d_counts.get(),
                                       d_ctrl_counts.get(), d_ctrl_ltot.get(), Global::discriminativePseudocount, d_bgprob.get(),
                                       d_expected.get(), d_logp.get(), d_z.get()),
@@ -169,6 +183,11 @@ BasePattern::BasePattern(const size_t pattern_length, Strand s, const int k, con
         d_ctrl_counts.download(c.data(), NP);
         dump("ctrl_counts.u32", c.data(), NP * sizeof(uint32_t));
         meta += "ctrl_ltot " + std::to_string(ctrl_ltot) + "\n";
+      }
+      if (strata) {
+        meta += "strata " + std::to_string(strata->G);
+        for (uint64_t w : strata->windows) meta += " " + std::to_string(w);
+        meta += "\n";
       }
       dump("meta.txt", meta.data(), meta.size());
     }

@@ -24,6 +24,7 @@
 #include "motif_holdout.h"
 #include "motif_match.h"
 #include "motif_positional.h"
+#include "motif_strata.h"
 #include "motif_refine.h"
 #include "motif_spacing.h"
 #include "motif_sites.h"
@@ -162,6 +163,25 @@ int main(int nargs, char** args) {
                      Global::positionalFilename);
     clock.lap("positional");
   }
+  // --stratified-background: the sweep's null becomes the mixture of the GC strata's models, weighted by the windows of
+  // what round 1 counts -- the training share, behind the mask; the rounds of --erase keep it
+  StratifiedNull stratified;
+  if (Global::stratifiedBackground && Global::patternLength >= PENGK_MIN_W && Global::patternLength <= PENGK_MAX_W &&
+      Global::patternLength % 2 == 0) {
+    if (!scan) {
+      scan.reset(new ScanInput);
+      build_scan_input(*Global::inputSequenceSet, scan.get());
+    }
+    StratifiedSettings ss;
+    ss.gc_bins = Global::stratifiedGcBins;
+    ss.min_bases = Global::stratifiedMinBases;
+    ss.report_path = Global::stratifiedReportFilename;
+    build_stratified_null(*scan, lc_mask.erase_valid(), holdout.attached ? &training : nullptr,
+                          Global::backgroundSequenceSet != Global::inputSequenceSet ? Global::backgroundSequenceSet : nullptr,
+                          Global::patternLength, *bgModel, ss, &stratified);
+    pengk_host::set_stratified_null(&stratified);
+    clock.lap("stratified background");
+  }
   Peng peng(Global::strand, Global::bgModelOrder, Global::maxOptBgModelOrder, Global::inputSequenceSet, bgModel);
 
   PengParameters params;
@@ -208,6 +228,7 @@ int main(int nargs, char** args) {
     clock.lap("erase rounds");
   }
   if (lc_mask.control_attached || holdout.control_attached) pengk_host::override_control_input(nullptr, nullptr);
+  pengk_host::set_stratified_null(nullptr);
   if (holdout.attached) pengk_host::override_sequence_count(nullptr, 0);
   // (--enrich scores against the negatives of --score-motifs and --dinuc: with it they are built once, for all three)
   // (--score-negatives control: the control set, matched to the input, serves whichever of the three is asked for)

@@ -136,7 +136,20 @@ BackgroundModel::~BackgroundModel() {
 // beyond 2^31 bases (BASELINE configs[3]: 2e10).  Here they are 64-bit and converted to float directly: bit-identical
 // to the reference while every counter fits an int, the intended arithmetic beyond (documented like the 64-bit scan
 // positions of the count; the device's pengk_bg_model does the same).
-void BackgroundModel::calculateV() {
+void BackgroundModel::calculateV() { calculateV(n_, v_, K_, A_, interpolate_); }
+
+void BackgroundModel::modelOf(const long long* counts84, int order, const std::vector<float>& alpha, bool interpolate, float* V84) {
+  long long n84[84];
+  for (int y = 0; y < 84; ++y) {
+    n84[y] = counts84[y];
+    V84[y] = 0.0f;
+  }
+  long long* n[3] = {n84, n84 + 4, n84 + 20};
+  float* v[3] = {V84, V84 + 4, V84 + 20};
+  calculateV(n, v, order, alpha, interpolate);
+}
+
+void BackgroundModel::calculateV(long long* const n_[3], float* const v_[3], int K_, const std::vector<float>& A_, bool interpolate_) {
   long long base_counts = 0;
   for (int y = 0; y < 4; ++y) base_counts += n_[0][y];
   for (int y = 0; y < 4; ++y) v_[0][y] = ((float)n_[0][y] + A_[0] * 0.25f) / ((float)base_counts + A_[0]);

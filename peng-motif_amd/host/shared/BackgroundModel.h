@@ -23,10 +23,15 @@ class BackgroundModel {
   int getOrder() { return K_; }
   float** getV() { return v_; }
   const long long* getCounts(int k) const { return n_[k]; }  // (k+1)-mer counts, BaMM (big-endian) ids
+  // calculateV on counters that are complete as they stand (84 values, orders 0..2 back to back, already summed over the
+  // ranks): V84 receives the conditional probabilities of orders 0..order, zeros beyond (--stratified-background: a
+  // stratum's model)
+  static void modelOf(const long long* counts84, int order, const std::vector<float>& alpha, bool interpolate, float* V84);
 
  private:
   void init(SequenceSet& sequenceSet, int order, std::vector<float> alpha, bool interpolate);
   void calculateV();
+  static void calculateV(long long* const n[3], float* const v[3], int K, const std::vector<float>& A, bool interpolate);
   std::string name_;
   int K_;
   std::vector<float> A_;
