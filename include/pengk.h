@@ -842,6 +842,33 @@ typedef struct {
  * array calls again.  Nt = 0 reports nothing.  PENGK_ERR_ARG: K, n_bins or both_strands as above, max_evalue not > 0. */
 int pengk_position_summary(const uint64_t* h_counts, int K, int n_bins, int both_strands, uint64_t min_count, double max_evalue,
                            pengk_position_word* out, uint64_t capacity, uint64_t* n_out);
+/* ---- the composition null of the positional report (--positional-null composition: q[b] above assumes that every bin has
+ *      the same composition; where a promoter grows G+C-richer towards its TSS, or a peak towards its summit, a bin lifts
+ *      every word made of its own letters.  Here each word's share per bin is tilted by what the bin's letters make of the
+ *      word) -- this project's own definitions again, not RSAT's numbers.
+ * Pair table.  d_pairs[b * 16 + 4 x + y] (n_bins x 16 uint64, ADDED to, caller-zeroed, as d_counts).  Every position p at
+ * which a word stands -- K consecutive valid bases from p on: ALL standing words, not only clump heads -- whose bin
+ * b = coordinate(p) / bin_size (the coordinates of pengk_position_count) is < n_bins adds 1 at x = s[p], y = s[p+1] and, with
+ * both_strands, 1 more at x = 3 - s[p+K-1], y = 3 - s[p+K-2]: the first pair of the word read on the other strand.  The sum
+ * of row b is 1 x / 2 x the standing words of bin b; n1[b][x] = sum_y pairs[b][4 x + y].  The same arguments, argument
+ * errors, n_seq = 0 behaviour and stream contract as pengk_position_count. */
+int pengk_position_pairs(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_valid, const int64_t* d_offs,
+                         const uint32_t* d_lens, uint64_t n_seq, int K, int anchor, int bin_size, int n_bins, int both_strands,
+                         uint64_t* d_pairs /* n_bins x 16, ADDED to */);
+/* Pure CPU.  h_pairs = NULL: pengk_position_summary, byte for byte.  Otherwise the same report with a share q_key[b] of
+ * its own for every key in place of q[b]; all of it in fp64, in exactly this order:
+ *   T_b[x][y] = (double)(pairs[b][4 x + y] + 1) / (double)(n1[b][x] + 4)        (an n1[b][x] = 0 row: 1/4 each)
+ *   f_b[x]    = (double)n1[b][x] / (double)(sum_x n1[b][x])
+ *   P_b(w)    = f_b[w_0], then *= T_b[w_i][w_i+1] for i = 0 .. K-2, left to right (w_0 the first base)
+ *   with both_strands P_b(key) = P_b(key) + P_b(revcomp(key)); a bin without a pair has P_b = 0
+ *   g_b = (double)N[b] * P_b(key);  G = the sum of g_b over b ascending;  q_key[b] = g_b / G
+ * A key with G = 0 is skipped (a counted word's first pair lies in its bin, so this happens on constructed tables only).
+ * expected = (double)C[key] * q_key[b], log10_pvalue = pengk_binomial_log10_sf(C[key], count, q_key[b]); candidates, the
+ * number of tests, the order, the tie-breaks, bins_significant and the families are those of pengk_position_summary.  Where
+ * every bin has the same pair frequencies this is the flat null up to rounding.  The same argument errors. */
+int pengk_position_summary_null(const uint64_t* h_counts, const uint64_t* h_pairs /* n_bins x 16, or NULL */, int K, int n_bins,
+                                int both_strands, uint64_t min_count, double max_evalue, pengk_position_word* out, uint64_t capacity,
+                                uint64_t* n_out);
 
 /* ---- motif refinement (--refine: the found motifs re-estimated and extended from their sites, as MEME, HOMER and STREME
  *      end) -------------------------------------------------------------------------------------------

@@ -42,7 +42,7 @@ EXPORTS = [
     "pengk_motif_enrich", "pengk_hypergeom_log10_sf", "pengk_enrich_summary",
     "pengk_motif_best_sites", "pengk_centrality_histograms", "pengk_centrality_summary", "pengk_binomial_log10_sf",
     "pengk_dyad_count", "pengk_dyad_summary",
-    "pengk_position_count", "pengk_position_summary",
+    "pengk_position_count", "pengk_position_summary", "pengk_position_pairs", "pengk_position_summary_null",
     "pengk_site_profiles", "pengk_profile_refine",
     "pengk_site_pair_profiles", "pengk_dinuc_model", "pengk_motif_scan_dinuc",
     "pengk_spacing_histograms", "pengk_spacing_summary",
@@ -223,6 +223,8 @@ def lib():
         L.pengk_dyad_summary.argtypes = [vp, vp, C.c_int, C.c_int, u64, C.c_double, vp, u64, C.POINTER(u64)]
         L.pengk_position_count.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
         L.pengk_position_summary.argtypes = [vp, C.c_int, C.c_int, C.c_int, u64, C.c_double, vp, u64, C.POINTER(u64)]
+        L.pengk_position_pairs.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
+        L.pengk_position_summary_null.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, u64, C.c_double, vp, u64, C.POINTER(u64)]
         L.pengk_site_profiles.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, vp, vp, vp, vp, C.c_int, vp]
         L.pengk_profile_refine.argtypes = [vp, C.c_int, C.c_int, vp, C.c_double, vp, vp, vp, C.POINTER(C.c_int32),
                                            C.POINTER(C.c_int32), C.POINTER(u64)]
@@ -373,21 +375,25 @@ def dyad_summary(counts, mono, both, min_count=5, max_evalue=0.01, capacity=None
     return [{k: getattr(out[i], k) for k, _ in DyadStruct._fields_} for i in range(n.value)]
 
 
-def position_summary(counts, K, both, min_count=5, max_evalue=0.01, capacity=None):
+def position_summary(counts, K, both, min_count=5, max_evalue=0.01, capacity=None, pairs=None):
     """the --positional report from the summed table of Context.position_count (pengk_position_summary, CPU): a list of
     dicts with key, bin, count, total, bin_positions, expected, log10_pvalue, log10_evalue, bins_significant, family,
     is_head, in report order.  capacity: the lines the first call has room for (a test hook: the call is repeated when
-    there are more)."""
+    there are more).  pairs: the summed n_bins x 16 table of Context.position_pairs -- the composition null
+    (pengk_position_summary_null) instead of the flat one."""
     c = np.ascontiguousarray(counts, np.uint64)
     assert c.ndim == 2
     if POSITION_MIN_K <= int(K) <= POSITION_MAX_K:
         assert c.shape[1] == 4 ** int(K)
+    if pairs is not None:
+        pairs = np.ascontiguousarray(pairs, np.uint64)
+        assert pairs.shape == (c.shape[0], 16)
     n = C.c_uint64()
     cap = 256 if capacity is None else int(capacity)
     while True:
         out = (PositionWordStruct * max(cap, 1))()
-        _check(lib().pengk_position_summary(c.ctypes.data, int(K), c.shape[0], int(both), int(min_count), float(max_evalue),
-                                            C.addressof(out), cap, C.byref(n)))
+        _check(lib().pengk_position_summary_null(c.ctypes.data, None if pairs is None else pairs.ctypes.data, int(K), c.shape[0], int(both),
+                                                 int(min_count), float(max_evalue), C.addressof(out), cap, C.byref(n)))
         if n.value <= cap:
             break
         cap = n.value
@@ -931,6 +937,16 @@ class Context:
                                           scan[4] if n_seq is None else n_seq, int(K), int(anchor), int(bin_size), int(n_bins),
                                           int(both), _ptr(counts)))
         return counts
+
+    def position_pairs(self, scan, K, anchor, bin_size, n_bins, both, all_valid=False, pairs=None, n_seq=None):
+        """the n_bins x 16 table of the first pairs of the words standing in each position bin of `scan`, on the device
+        (pengk_position_pairs): the arguments of position_count; pairs: a device uint64 array to ADD to."""
+        if pairs is None:
+            pairs = self.to_device(np.zeros((max(1, min(int(n_bins), POSITION_MAX_BINS)), 16), np.uint64))
+        _check(lib().pengk_position_pairs(self.h, _ptr(scan[0]), None if all_valid else _ptr(scan[1]), _ptr(scan[2]), _ptr(scan[3]),
+                                          scan[4] if n_seq is None else n_seq, int(K), int(anchor), int(bin_size), int(n_bins),
+                                          int(both), _ptr(pairs)))
+        return pairs
 
     def pack_scan(self, scan, W, item_windows=0, valid=None, all_valid=False, attach=False):
         """the sequences of `scan` (under the validity words `valid` instead of its own, when given) in the count layout,

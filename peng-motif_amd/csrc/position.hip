@@ -289,6 +289,180 @@ int pos_launch(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_valid,
   return PENGK_OK;
 }
 
+// ---- the pair table (--positional-null composition) -------------------------------------------------------
+// The same tiles in the same static shares.  A position's bin is decided in the lane as in the count; what it adds is one of
+// 16 pair values (two on both strands), and a poly-A run is 64 lanes on one counter: no lane adds for itself.  The lanes of a
+// tile are consecutive positions, so a bin is a run of lanes (two under the centre anchor): the first lane of a run takes
+// the run's lane mask, the wave ballots each pair value that occurs in the tile, and the run's first lane adds the popcount
+// of ballot & mask to its bin's counter -- at most 16 LDS adds a lane and tile, each by the few lanes that begin a run, none
+// where the value does not occur.  One table of n_bins x 16 uint32 a workgroup (4 KiB at most), shared by its waves.
+constexpr uint32_t POS_PAIR_FLUSH_ROUNDS = 1u << 20;  // x 1024 positions a round x 2 strands = 2^31 per counter at most
+constexpr uint32_t POS_NO_BIN = 0xFFFFFFFFu;
+
+template <int K, bool BOTH>
+__device__ __forceinline__ void pos_pair_tile(const uint64_t* __restrict__ wp, const uint32_t* __restrict__ vp, uint32_t L, uint32_t k,
+                                              int anchor, uint32_t S, uint32_t R, uint32_t* tab) {
+  constexpr uint32_t ALL = (1u << K) - 1u;
+  const uint32_t D = L - (uint32_t)K;  // the last position
+  const uint32_t P0 = k << 6;          // (k < 2^26)
+  if (P0 > D) return;
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t p = P0 + lane;
+  // the 16 bases and the validity bits of the 32 bases from p on: the word at p is the first K <= 7 of them
+  const uint32_t* hp = reinterpret_cast<const uint32_t*>(wp);
+  const uint32_t nh = (L + 15u) >> 4, h = p >> 4;
+  const uint32_t H0 = h < nh ? hp[h] : 0u, H1 = h + 1u < nh ? hp[h + 1u] : 0u;
+  const uint32_t lo = __builtin_amdgcn_alignbit(H1, H0, (p & 15u) << 1);
+  const uint32_t nw = (L + 31u) >> 5, j = p >> 5;
+  const uint32_t V0 = pos_valid_word(vp, L, nw, j), V1 = pos_valid_word(vp, L, nw, j + 1u);
+  const uint32_t v = __builtin_amdgcn_alignbit(V1, V0, p & 31u);
+  const uint32_t c = p <= D ? pos_coordinate(anchor, p, D) : R;
+  const uint32_t bin = c < R ? c / S : POS_NO_BIN;
+  const bool on = bin != POS_NO_BIN && (v & ALL) == ALL;  // (a word that stands ends inside the sequence: p <= D)
+  if (__builtin_amdgcn_ballot_w64(on) == 0ull) return;
+  const uint32_t fwd = ((lo & 3u) << 2) | ((lo >> 2) & 3u);                                                   // 4 s[p] + s[p+1]
+  const uint32_t rev = (((~lo >> (2 * (K - 1))) & 3u) << 2) | ((~lo >> (2 * (K - 2))) & 3u);  // 4 (3 - s[p+K-1]) + 3 - s[p+K-2]
+  // runs of one bin: a lane begins one where the lane before it has another bin
+  const uint32_t before = (uint32_t)__shfl_up((int)bin, 1);
+  const bool first = lane == 0u || before != bin;
+  const uint64_t firsts = __builtin_amdgcn_ballot_w64(first);
+  const uint64_t behind = lane == 63u ? 0ull : firsts & ~((2ull << lane) - 1ull);  // the runs that begin behind this lane
+  const uint32_t next = behind ? (uint32_t)__builtin_ctzll(behind) : 64u;
+  const uint64_t upto = next == 64u ? ~0ull : (1ull << next) - 1ull;
+  const uint64_t run = upto & ~((1ull << lane) - 1ull);  // the lanes [lane, next)
+  const bool adds = first && bin != POS_NO_BIN;
+  uint32_t* row = tab + ((adds ? bin : 0u) << 4);
+#pragma unroll
+  for (uint32_t x = 0; x < 16u; ++x) {
+    const uint64_t mf = __builtin_amdgcn_ballot_w64(on && fwd == x);
+    const uint64_t mr = BOTH ? __builtin_amdgcn_ballot_w64(on && rev == x) : 0ull;
+    if ((mf | mr) == 0ull) continue;  // (wave-uniform)
+    const uint32_t n = (uint32_t)__builtin_popcountll(mf & run) + (BOTH ? (uint32_t)__builtin_popcountll(mr & run) : 0u);
+    if (adds && n) atomicAdd(&row[x], n);
+  }
+}
+
+__device__ __forceinline__ void pos_pair_flush(uint32_t* tab, int n, unsigned long long* __restrict__ pairs) {
+  __syncthreads();
+  for (int q = threadIdx.x; q < n; q += POS_THREADS) {
+    const uint32_t c = tab[q];
+    if (c) {
+      tab[q] = 0u;
+      atomicAdd(&pairs[q], (unsigned long long)c);
+    }
+  }
+  __syncthreads();
+}
+
+template <int K, bool BOTH>
+__global__ __launch_bounds__(POS_THREADS) void pos_pairs_kernel(const uint64_t* __restrict__ words, const uint32_t* __restrict__ valid,
+                                                                const int64_t* __restrict__ offs, const uint32_t* __restrict__ lens,
+                                                                uint64_t n_seq, int anchor, uint32_t S, int n_bins,
+                                                                const unsigned long long* __restrict__ excl,
+                                                                const unsigned long long* __restrict__ boff, uint64_t n_groups,
+                                                                unsigned long long* __restrict__ pairs) {
+  __shared__ uint32_t tab[PENGK_POSITION_MAX_BINS * 16];
+  const int n_tab = n_bins * 16;
+  const uint32_t R = (uint32_t)n_bins * S;
+  // this wave's share of the tiles, as in pos_count_kernel: [g, gend); `per` rounds for every wave of the grid
+  const uint64_t total = boff[n_groups];
+  const uint64_t n_waves = (uint64_t)gridDim.x * POS_WAVES;
+  const uint64_t per = (total + n_waves - 1) / n_waves;
+  if ((uint64_t)blockIdx.x * POS_WAVES * per >= total) return;  // (the whole workgroup)
+  for (int q = threadIdx.x; q < n_tab; q += POS_THREADS) tab[q] = 0u;
+  __syncthreads();
+  const uint64_t wave = (uint64_t)blockIdx.x * POS_WAVES + (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  uint64_t g = wave * per;
+  const uint64_t gend = g + per < total ? g + per : total;
+  uint64_t i = 0;
+  uint32_t k = 0, L = 0;
+  PosTiles t = {0u, 0u};
+  if (g < gend) {
+    uint64_t lo = 0, hi = n_groups;  // boff[lo] <= g < boff[hi]
+    while (hi - lo > 1) {
+      const uint64_t mid = lo + (hi - lo) / 2;
+      if (boff[mid] <= g) lo = mid;
+      else hi = mid;
+    }
+    const uint64_t rest = g - boff[lo];
+    i = lo * POS_SCAN_THREADS;
+    uint64_t ihi = std::min<uint64_t>(n_seq, i + POS_SCAN_THREADS);
+    while (ihi - i > 1) {
+      const uint64_t mid = i + (ihi - i) / 2;
+      if (excl[mid] <= rest) i = mid;
+      else ihi = mid;
+    }
+    k = (uint32_t)(rest - excl[i]);
+    L = lens[i];
+    t = pos_tiles(L, K, anchor, R);
+  }
+  uint32_t since = 0;
+  for (uint64_t round = 0; round < per; ++round) {  // (per, and so every barrier below, is the same for the whole grid)
+    if (g < gend) {
+      while (k >= t.nt) {  // the next sequence that has a tile (there is one: g < total)
+        if (++i >= n_seq) break;
+        L = lens[i];
+        t = pos_tiles(L, K, anchor, R);
+        k = 0;
+      }
+      if (i < n_seq) {
+        const uint64_t w0 = (uint64_t)offs[i] >> 5;
+        pos_pair_tile<K, BOTH>(words + w0, valid ? valid + w0 : nullptr, L, t.k0 + k, anchor, S, R, tab);
+      }
+      ++k;
+      ++g;
+    }
+    if (++since == POS_PAIR_FLUSH_ROUNDS) {
+      pos_pair_flush(tab, n_tab, pairs);
+      since = 0;
+    }
+  }
+  if (since) pos_pair_flush(tab, n_tab, pairs);
+}
+
+template <int K, bool BOTH>
+int pos_pairs_launch(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_valid, const int64_t* d_offs, const uint32_t* d_lens,
+                     uint64_t n_seq, int anchor, uint32_t S, int n_bins, const unsigned long long* excl, const unsigned long long* boff,
+                     uint64_t n_groups, uint64_t* d_pairs) {
+  const dim3 grid((unsigned)ctx->num_cu * 2u);  // (32 waves a CU: two workgroups of 1024 threads)
+  hipLaunchKernelGGL((pos_pairs_kernel<K, BOTH>), grid, dim3(POS_THREADS), 0, ctx->stream, d_words, d_valid, d_offs, d_lens, n_seq, anchor,
+                     S, n_bins, excl, boff, n_groups, (unsigned long long*)d_pairs);
+  PENGK_HIP(hipGetLastError());
+  return PENGK_OK;
+}
+
+// the argument checks, enter(ctx) and the two prefix-sum launches that pengk_position_count and pengk_position_pairs share:
+// scratch = excl (n_seq uint64) | boff (n_groups + 1 uint64)
+struct PosPlan {
+  unsigned long long *excl, *boff;
+  uint64_t n_groups;
+};
+int pos_prepare(pengk_ctx* ctx, const char* fn, const uint64_t* d_words, const int64_t* d_offs, const uint32_t* d_lens, uint64_t n_seq, int K,
+                int anchor, int bin_size, int n_bins, int both_strands, const uint64_t* d_table, PosPlan* plan) {
+  if (!ctx || (n_seq && (!d_words || !d_offs || !d_lens || !d_table))) return fail(PENGK_ERR_ARG, "%s: bad argument", fn);
+  if (K < PENGK_POSITION_MIN_K || K > PENGK_POSITION_MAX_K)
+    return fail(PENGK_ERR_ARG, "%s: K %d out of range [%d,%d]", fn, K, PENGK_POSITION_MIN_K, PENGK_POSITION_MAX_K);
+  if (anchor < 0 || anchor > 2) return fail(PENGK_ERR_ARG, "%s: anchor must be 0 (start), 1 (end) or 2 (centre)", fn);
+  if (bin_size < 1 || bin_size > PENGK_POSITION_MAX_BIN_SIZE)
+    return fail(PENGK_ERR_ARG, "%s: bin_size %d out of range [1,%d]", fn, bin_size, PENGK_POSITION_MAX_BIN_SIZE);
+  if (n_bins < 1 || n_bins > PENGK_POSITION_MAX_BINS)
+    return fail(PENGK_ERR_ARG, "%s: n_bins %d out of range [1,%d]", fn, n_bins, PENGK_POSITION_MAX_BINS);
+  if (both_strands != 0 && both_strands != 1) return fail(PENGK_ERR_ARG, "%s: both_strands must be 0 or 1", fn);
+  if (n_seq >> 32) return fail(PENGK_ERR_ARG, "%s: 2^32 sequences or more; shard the input", fn);
+  int rc = enter(ctx);
+  if (rc) return rc;
+  if (n_seq == 0) return PENGK_OK;
+  plan->n_groups = (n_seq + POS_SCAN_THREADS - 1) / POS_SCAN_THREADS;
+  rc = ensure_scratch(ctx, &ctx->d_sites, &ctx->sites_bytes, (n_seq + plan->n_groups + 1) * sizeof(uint64_t));
+  if (rc) return rc;
+  plan->excl = (unsigned long long*)ctx->d_sites;
+  plan->boff = plan->excl + n_seq;
+  hipLaunchKernelGGL(pos_tiles_kernel, dim3((unsigned)plan->n_groups), dim3(POS_SCAN_THREADS), 0, ctx->stream, d_lens, n_seq, K, anchor,
+                     (uint32_t)bin_size * (uint32_t)n_bins, plan->excl, plan->boff);
+  hipLaunchKernelGGL(pos_groups_kernel, dim3(1), dim3(POS_SCAN_THREADS), 0, ctx->stream, plan->boff, plan->n_groups);
+  return PENGK_OK;
+}
+
 inline uint64_t pos_keys(int K, int both) {
   const uint64_t all = 1ull << (2 * K);
   if (!both) return all;
@@ -304,34 +478,16 @@ extern "C" {
 
 int pengk_position_count(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_valid, const int64_t* d_offs, const uint32_t* d_lens,
                          uint64_t n_seq, int K, int anchor, int bin_size, int n_bins, int both_strands, uint64_t* d_counts) {
-  if (!ctx || (n_seq && (!d_words || !d_offs || !d_lens || !d_counts))) return fail(PENGK_ERR_ARG, "pengk_position_count: bad argument");
-  if (K < PENGK_POSITION_MIN_K || K > PENGK_POSITION_MAX_K)
-    return fail(PENGK_ERR_ARG, "pengk_position_count: K %d out of range [%d,%d]", K, PENGK_POSITION_MIN_K, PENGK_POSITION_MAX_K);
-  if (anchor < 0 || anchor > 2) return fail(PENGK_ERR_ARG, "pengk_position_count: anchor must be 0 (start), 1 (end) or 2 (centre)");
-  if (bin_size < 1 || bin_size > PENGK_POSITION_MAX_BIN_SIZE)
-    return fail(PENGK_ERR_ARG, "pengk_position_count: bin_size %d out of range [1,%d]", bin_size, PENGK_POSITION_MAX_BIN_SIZE);
-  if (n_bins < 1 || n_bins > PENGK_POSITION_MAX_BINS)
-    return fail(PENGK_ERR_ARG, "pengk_position_count: n_bins %d out of range [1,%d]", n_bins, PENGK_POSITION_MAX_BINS);
-  if (both_strands != 0 && both_strands != 1) return fail(PENGK_ERR_ARG, "pengk_position_count: both_strands must be 0 or 1");
-  if (n_seq >> 32) return fail(PENGK_ERR_ARG, "pengk_position_count: 2^32 sequences or more; shard the input");
-  int rc = enter(ctx);
-  if (rc) return rc;
-  if (n_seq == 0) return PENGK_OK;
-  const uint64_t n_groups = (n_seq + POS_SCAN_THREADS - 1) / POS_SCAN_THREADS;
-  // scratch: excl (n_seq uint64) | boff (n_groups + 1 uint64)
-  rc = ensure_scratch(ctx, &ctx->d_sites, &ctx->sites_bytes, (n_seq + n_groups + 1) * sizeof(uint64_t));
-  if (rc) return rc;
-  unsigned long long* excl = (unsigned long long*)ctx->d_sites;
-  unsigned long long* boff = excl + n_seq;
-  hipLaunchKernelGGL(pos_tiles_kernel, dim3((unsigned)n_groups), dim3(POS_SCAN_THREADS), 0, ctx->stream, d_lens, n_seq, K, anchor,
-                     (uint32_t)bin_size * (uint32_t)n_bins, excl, boff);
-  hipLaunchKernelGGL(pos_groups_kernel, dim3(1), dim3(POS_SCAN_THREADS), 0, ctx->stream, boff, n_groups);
-#define PENGK_POS_CASE(k)                                                                                                          \
-  case k:                                                                                                                          \
-    return both_strands ? pos_launch<k, true>(ctx, d_words, d_valid, d_offs, d_lens, n_seq, anchor, (uint32_t)bin_size, n_bins, excl,  \
-                                              boff, n_groups, d_counts)                                                            \
-                        : pos_launch<k, false>(ctx, d_words, d_valid, d_offs, d_lens, n_seq, anchor, (uint32_t)bin_size, n_bins, excl, \
-                                               boff, n_groups, d_counts)
+  PosPlan plan;
+  const int rc = pos_prepare(ctx, "pengk_position_count", d_words, d_offs, d_lens, n_seq, K, anchor, bin_size, n_bins, both_strands, d_counts,
+                             &plan);
+  if (rc || n_seq == 0) return rc;
+#define PENGK_POS_CASE(k)                                                                                                               \
+  case k:                                                                                                                               \
+    return both_strands ? pos_launch<k, true>(ctx, d_words, d_valid, d_offs, d_lens, n_seq, anchor, (uint32_t)bin_size, n_bins, plan.excl,  \
+                                              plan.boff, plan.n_groups, d_counts)                                                       \
+                        : pos_launch<k, false>(ctx, d_words, d_valid, d_offs, d_lens, n_seq, anchor, (uint32_t)bin_size, n_bins, plan.excl, \
+                                               plan.boff, plan.n_groups, d_counts)
   switch (K) {
     PENGK_POS_CASE(4);
     PENGK_POS_CASE(5);
@@ -342,8 +498,30 @@ int pengk_position_count(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t
   return PENGK_OK;
 }
 
-int pengk_position_summary(const uint64_t* h_counts, int K, int n_bins, int both_strands, uint64_t min_count, double max_evalue,
-                           pengk_position_word* out, uint64_t capacity, uint64_t* n_out) {
+int pengk_position_pairs(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_valid, const int64_t* d_offs, const uint32_t* d_lens,
+                         uint64_t n_seq, int K, int anchor, int bin_size, int n_bins, int both_strands, uint64_t* d_pairs) {
+  PosPlan plan;
+  const int rc = pos_prepare(ctx, "pengk_position_pairs", d_words, d_offs, d_lens, n_seq, K, anchor, bin_size, n_bins, both_strands, d_pairs,
+                             &plan);
+  if (rc || n_seq == 0) return rc;
+#define PENGK_POS_CASE(k)                                                                                                                     \
+  case k:                                                                                                                                     \
+    return both_strands ? pos_pairs_launch<k, true>(ctx, d_words, d_valid, d_offs, d_lens, n_seq, anchor, (uint32_t)bin_size, n_bins, plan.excl,  \
+                                                    plan.boff, plan.n_groups, d_pairs)                                                        \
+                        : pos_pairs_launch<k, false>(ctx, d_words, d_valid, d_offs, d_lens, n_seq, anchor, (uint32_t)bin_size, n_bins, plan.excl, \
+                                                     plan.boff, plan.n_groups, d_pairs)
+  switch (K) {
+    PENGK_POS_CASE(4);
+    PENGK_POS_CASE(5);
+    PENGK_POS_CASE(6);
+    PENGK_POS_CASE(7);
+  }
+#undef PENGK_POS_CASE
+  return PENGK_OK;
+}
+
+int pengk_position_summary_null(const uint64_t* h_counts, const uint64_t* h_pairs, int K, int n_bins, int both_strands, uint64_t min_count,
+                                double max_evalue, pengk_position_word* out, uint64_t capacity, uint64_t* n_out) {
   if (!h_counts || !n_out || (capacity && !out)) return fail(PENGK_ERR_ARG, "pengk_position_summary: bad argument");
   if (K < PENGK_POSITION_MIN_K || K > PENGK_POSITION_MAX_K)
     return fail(PENGK_ERR_ARG, "pengk_position_summary: K %d out of range [%d,%d]", K, PENGK_POSITION_MIN_K, PENGK_POSITION_MAX_K);
@@ -365,11 +543,56 @@ int pengk_position_summary(const uint64_t* h_counts, int K, int n_bins, int both
   if (Nt == 0) return PENGK_OK;
   std::vector<double> q((size_t)n_bins);
   for (int b = 0; b < n_bins; ++b) q[b] = (double)N[b] / (double)Nt;
+  // the composition null: a bin's first-order chain from its pair table -- f[x], T[x][y] --, a word's probability under it
+  std::vector<double> chain_f, chain_T;
+  std::vector<char> chain_has;
+  if (h_pairs) {
+    chain_f.assign((size_t)n_bins * 4, 0.0);
+    chain_T.assign((size_t)n_bins * 16, 0.0);
+    chain_has.assign((size_t)n_bins, 0);
+    for (int b = 0; b < n_bins; ++b) {
+      uint64_t n1[4] = {0, 0, 0, 0}, all = 0;
+      for (int x = 0; x < 4; ++x)
+        for (int y = 0; y < 4; ++y) n1[x] += h_pairs[(size_t)b * 16 + 4 * x + y];
+      for (int x = 0; x < 4; ++x) all += n1[x];
+      if (all == 0) continue;
+      chain_has[b] = 1;
+      for (int x = 0; x < 4; ++x) {
+        chain_f[(size_t)b * 4 + x] = (double)n1[x] / (double)all;
+        for (int y = 0; y < 4; ++y)
+          chain_T[(size_t)b * 16 + 4 * x + y] = (double)(h_pairs[(size_t)b * 16 + 4 * x + y] + 1) / (double)(n1[x] + 4);
+      }
+    }
+  }
+  auto word_probability = [&](int b, uint32_t w) {
+    uint32_t x = (w >> (2 * (K - 1))) & 3u;
+    double P = chain_f[(size_t)b * 4 + x];
+    for (int i = 1; i < K; ++i) {
+      const uint32_t y = (w >> (2 * (K - 1 - i))) & 3u;
+      P *= chain_T[(size_t)b * 16 + 4 * x + y];
+      x = y;
+    }
+    return P;
+  };
   const double log_tests = std::log10((double)((uint64_t)n_bins * pos_keys(K, both_strands)));
   const double log_max = std::log10(max_evalue);
   std::vector<pengk_position_word> rep;
   for (uint32_t key = 0; key < NK; ++key) {
     if (C[key] == 0) continue;
+    if (h_pairs) {  // q[b] of this key: its shares g_b / G
+      double G = 0.0;
+      for (int b = 0; b < n_bins; ++b) {
+        double P = 0.0;
+        if (chain_has[b]) {
+          P = word_probability(b, key);
+          if (both_strands) P = P + word_probability(b, revcomp32(key, K));
+        }
+        q[b] = (double)N[b] * P;
+        G += q[b];
+      }
+      if (G == 0.0) continue;
+      for (int b = 0; b < n_bins; ++b) q[b] = q[b] / G;
+    }
     pengk_position_word best = {};
     bool have = false;
     uint32_t significant = 0;
@@ -449,6 +672,11 @@ int pengk_position_summary(const uint64_t* h_counts, int K, int n_bins, int both
   *n_out = rep.size();
   for (size_t k = 0; k < rep.size() && k < capacity; ++k) out[k] = rep[k];
   return PENGK_OK;
+}
+
+int pengk_position_summary(const uint64_t* h_counts, int K, int n_bins, int both_strands, uint64_t min_count, double max_evalue,
+                           pengk_position_word* out, uint64_t capacity, uint64_t* n_out) {
+  return pengk_position_summary_null(h_counts, nullptr, K, n_bins, both_strands, min_count, max_evalue, out, capacity, n_out);
 }
 
 }  // extern "C"

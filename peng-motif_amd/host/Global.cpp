@@ -101,6 +101,7 @@ int Global::positionalBinSize = 10;
 int Global::positionalBins = 20;
 double Global::positionalEvalue = 0.01;
 unsigned long long Global::positionalMinCount = 5;
+bool Global::positionalCompositionNull = false;
 bool Global::stratifiedBackground = false;
 int Global::stratifiedGcBins = 10;
 unsigned long long Global::stratifiedMinBases = 10000;
@@ -627,6 +628,16 @@ void Global::readArguments(int nargs, char* args[]) {
       }
       positionalEvalue = x;
       positional_option = "--positional-evalue";
+    } else if (!strcmp(a, "--positional-null")) {
+      const char* v = need(i, nargs, args, printHelp);
+      if (!strcmp(v, "flat")) positionalCompositionNull = false;
+      else if (!strcmp(v, "composition")) positionalCompositionNull = true;
+      else {
+        printHelp();
+        log_line("ERROR", "--positional-null must be flat or composition");
+        exit(4);
+      }
+      positional_option = "--positional-null";
     } else if (!strcmp(a, "--stratified-background")) {
       stratifiedBackground = true;
     } else if (!strcmp(a, "--stratified-report")) {
@@ -803,6 +814,11 @@ void Global::printHelp() {
   printf("  --positional-bins INT          bins counted from the anchor on, 1..64 (default 20); words further out are ignored\n");
   printf("  --positional-evalue FLOAT      a word is reported at this E-value or below (default 0.01)\n");
   printf("  --positional-min-count INT     occurrences a word needs in its bin (default 5)\n");
+  printf("  --positional-null NAME         flat: a bin's share of a word is its share of all words (default).  composition: the\n");
+  printf("                                 share is tilted by what the bin's own letters make of the word -- a first-order chain\n");
+  printf("                                 from the first pairs of the bin's words, counted on the device --, for inputs whose\n");
+  printf("                                 composition changes along the sequence (promoters, peaks); FILE gets the column\n");
+  printf("                                 flat_expected\n");
   printf("  --stratified-background        score the k-mers against a GC-stratified null: the sequences are put into GC bins, every\n");
   printf("                                 bin gets a background model of its own (same order, alpha and interpolation) from the\n");
   printf("                                 background set's sequences of that bin, and a k-mer's probability is the mean of the\n");

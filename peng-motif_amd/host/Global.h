@@ -117,6 +117,7 @@ class Global {
   static int positionalBins;                 // --positional-bins: 1..PENGK_POSITION_MAX_BINS
   static double positionalEvalue;            // --positional-evalue
   static unsigned long long positionalMinCount;  // --positional-min-count
+  static bool positionalCompositionNull;     // --positional-null composition (new: each word held to its bin's letters)
   static bool stratifiedBackground;          // --stratified-background (new: a GC-stratified null for the k-mer sweep)
   static int stratifiedGcBins;               // --stratified-gc-bins: 1..16
   static unsigned long long stratifiedMinBases;  // --stratified-min-bases: a stratum with fewer model bases takes the global model

@@ -159,6 +159,7 @@ int main(int nargs, char** args) {
     ps.bins = Global::positionalBins;
     ps.evalue = Global::positionalEvalue;
     ps.min_count = Global::positionalMinCount;
+    ps.composition_null = Global::positionalCompositionNull;
     write_positional(*scan, lc_mask.erase_valid(), holdout.attached ? &training : nullptr, Global::strand == Strand::BOTH_STRANDS, ps,
                      Global::positionalFilename);
     clock.lap("positional");

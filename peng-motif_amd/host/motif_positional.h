@@ -17,6 +17,7 @@ struct PositionalSettings {
   int bins = 20;                     // --positional-bins: 1 .. PENGK_POSITION_MAX_BINS
   double evalue = 0.01;              // --positional-evalue: a word is reported at this E-value or below
   unsigned long long min_count = 5;  // --positional-min-count
+  bool composition_null = false;     // --positional-null composition: pengk_position_pairs and pengk_position_summary_null
 };
 
 // the word as letters, first base first
@@ -24,7 +25,9 @@ std::string positional_word_string(uint32_t key, int width);
 
 // pengk_position_count over this rank's records of `in` -- behind the validity words d_valid when given (the low-complexity
 // mask), over the subset `training` when given (--holdout) --, the table summed over the ranks, pengk_position_summary, and
-// the TSV at `path` (rank 0; one stdout line).  Collective in a multi-rank run.
+// the TSV at `path` (rank 0; one stdout line).  Under the composition null the pair table is counted over the same share
+// behind the same validity, summed likewise, and the TSV gets the column flat_expected behind expected.
+// Collective in a multi-rank run.
 void write_positional(const ScanInput& in, const uint32_t* d_valid, const ScanSubset* training, bool both_strands,
                       const PositionalSettings& ps, const char* path);
 
