@@ -275,6 +275,49 @@ int pengk_pattern_stats_strata(pengk_ctx* ctx, int W, int both_strands, int k, i
                                double pseudocount /* control: NULL, NULL, 0 = none */, float* d_bgprob, float* d_expected,
                                float* d_logp, float* d_z);
 
+/* ---- a Markov null of order 3 .. 5 for the sweep (--high-order-background: genomic sequence has structure beyond
+ *      trinucleotides, and an order-2 model under-predicts every word built of common 4-6-mers by an excess that grows with
+ *      the square root of the input; MEME-suite users pass an order 3-5 model from fasta-get-markov -m; INTEGRATION.md 7u,
+ *      DESIGN.md 29) ---------------------------------------------------------------------------------------------------
+ * This project's own definitions (the reference's model stops at order 2).  Integer counters, float32 in a stated order: a
+ * numpy restatement and any sharding give the same bits.  The tables of orders 0 .. K lie back to back, order k at
+ * at_k = (4^(k+1) - 4) / 3 = 0, 4, 20, 84, 340, 1364; K = 5 has (4^(K+2) - 4) / 3 = 5460 entries.
+ *
+ * The counters of a scan layout (the layout of pengk_motif_scan).  For every sequence, every position p and every order k in
+ * 0 .. K with p >= k: the (k+1)-mer ending at p is counted, d_bg[at_k + y] += 1, iff ALL of its k + 1 bases are valid (the
+ * rule of pengk_strata_bg_count: an invalid base takes part in no word of any order, and the base behind it starts over at
+ * order 0).  y: the word in BaMM order, older base more significant.  d_valid = NULL: every base valid.  d_bg is ADDED to
+ * (caller-zeroed): shards and several calls sum exactly; at K = 2 the counters are those of pengk_strata_bg_count with one
+ * stratum.  n_seq = 0 does nothing.  PENGK_ERR_ARG: K outside 0 .. 5, n_seq >= 2^32, a null pointer (but d_valid) with
+ * n_seq > 0.  Asynchronous on the context's stream: no host wait. */
+int pengk_bg_count_order(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_valid /* NULL: all valid */,
+                         const int64_t* d_offs, const uint32_t* d_lens, uint64_t n_seq, int K /* 0..5 */,
+                         uint64_t* d_bg /* (4^(K+2) - 4) / 3, ADDED to */);
+/* The model of those counters (host only): BackgroundModel::calculateV continued to order K, float32, the same operations
+ * in the same order.  V_0[y] = (n_0[y] + alpha_0 / 4) / (sum of n_0 + alpha_0); for k = 1 .. K
+ *     V_k[y] = (n_k[y] + alpha_k * prior) / (n_{k-1}[y / 4] + alpha_k),   prior = V_{k-1}[y mod 4^k] (interpolate) or 1/4,
+ * then every row of four is divided by its float32 sum (added in ascending order from 0).  h_alpha: K + 1 floats.  At
+ * K <= 2 on the same counters the bits of pengk_bg_model and of the host's BackgroundModel.  PENGK_ERR_ARG: K outside
+ * 0 .. 5, a null pointer. */
+int pengk_bg_model_order(const uint64_t* h_counts, int K, const float* h_alpha /* K + 1 */, int interpolate, float* h_V);
+/* The sweep with that model in its highest slot.  d_V: the run's own model, float[84] as pengk_pattern_stats takes it;
+ * d_VK: orders 0 .. K of the high-order model, (4^(K+2) - 4) / 3 floats.  Slots o < max_k of d_bgprob hold exactly what
+ * pengk_pattern_stats writes for d_V.  Slot max_k holds the order-K probability from d_VK: the factor of position
+ * i = 0 .. W-1 is V_c[x_{i-c} .. x_i] with c = min(i, K), the products float32 in position order starting 1.0f * v0; under
+ * both strands p[x] + p[rc x] in float32, a palindrome evaluated once.  At K = 2 with d_VK[0..84) == d_V and max_k = 2 every
+ * table has pengk_pattern_stats' bits.  With a control (d_ctrl_counts, d_ctrl_ltot, pseudocount as
+ * pengk_pattern_stats_control takes them; NULL, NULL, 0: none) every slot is q_o[x] = (float) fmax((double) p_o[x],
+ * share[x]).  Expected, log-p and z are made of slot k, d_ltot and d_counts exactly as pengk_pattern_stats makes them.
+ * Every even W from 2 to 14; the result does not depend on the option sweep_pairs.  PENGK_ERR_ARG: a NULL argument (but the
+ * control's), K outside 0 .. 5, orders as pengk_pattern_stats refuses them, one control pointer without the other, a
+ * pseudocount that is not finite and >= 0, or not 0 without a control.  Asynchronous on the context's stream: no host
+ * wait. */
+int pengk_pattern_stats_order(pengk_ctx* ctx, int W, int both_strands, int k, int max_k, const float* d_V /* 84 */,
+                              int K /* 0..5 */, const float* d_VK /* orders 0..K */, const uint64_t* d_ltot,
+                              const uint32_t* d_counts, const uint32_t* d_ctrl_counts, const uint64_t* d_ctrl_ltot,
+                              double pseudocount /* control: NULL, NULL, 0 = none */, float* d_bgprob, float* d_expected,
+                              float* d_logp, float* d_z);
+
 /* ---- seed candidates (first half of BasePattern::select_base_patterns, src/base_pattern.cpp:443-515) ----------------
  * The reference std::sorts all 4^W ids by z-score and walks the ranking down to the threshold (:458-466); only ids with
  * z >= z_threshold and count >= count_threshold can become seeds.  This call compacts exactly those on the device

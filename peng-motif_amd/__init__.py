@@ -27,6 +27,7 @@ EXPORTS = [
     "pengk_pack", "pengk_pack_threads", "pengk_pack_append", "pengk_packed_free", "pengk_set_sequences", "pengk_synth_sizes", "pengk_synth_sequences",
     "pengk_count", "pengk_count_bg", "pengk_mirror_counts", "pengk_bg_count", "pengk_bg_model", "pengk_pattern_stats", "pengk_pattern_stats_control",
     "pengk_strata_bg_count", "pengk_pattern_stats_strata",
+    "pengk_bg_count_order", "pengk_bg_model_order", "pengk_pattern_stats_order",
     "pengk_seed_candidates", "pengk_iupac_aggregate", "pengk_em", "pengk_em_device", "pengk_test_em_generation", "pengk_sequential_sum_f32", "pengk_motif_similarity", "pengk_selftest_division",
     "pengk_comm_unique_id", "pengk_comm_init", "pengk_comm_init_env", "pengk_comm_info", "pengk_comm_init_abandoned", "pengk_comm_rccl_version", "pengk_comm_destroy",
     "pengk_allreduce_tables", "pengk_comm_check_bin_bound", "pengk_allgather",
@@ -165,6 +166,9 @@ def lib():
         L.pengk_pattern_stats_control.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_double, vp, vp, vp, vp]
         L.pengk_strata_bg_count.argtypes = [vp, vp, vp, vp, vp, u64, vp, C.c_int, C.c_int, vp, vp]
         L.pengk_pattern_stats_strata.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, C.c_double, vp, vp, vp, vp]
+        L.pengk_bg_count_order.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, vp]
+        L.pengk_bg_model_order.argtypes = [vp, C.c_int, vp, C.c_int, vp]
+        L.pengk_pattern_stats_order.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, C.c_double, vp, vp, vp, vp]
         L.pengk_seed_candidates.argtypes = [vp, C.c_int, vp, vp, f32, u64, vp, vp, i64, C.POINTER(i64)]
         L.pengk_iupac_aggregate.argtypes = [vp, C.c_int, C.c_int, vp, i64, vp, vp, vp, vp]
         L.pengk_em.argtypes = [vp, C.c_int, i64, vp, f32, f32, C.c_int, vp, vp, vp, vp]
@@ -405,6 +409,21 @@ def hypergeom_log10_sf(N, K, n, k):
     out = C.c_double()
     _check(lib().pengk_hypergeom_log10_sf(int(N), int(K), int(n), int(k), C.byref(out)))
     return out.value
+
+
+def order_table_size(K):
+    """entries of the tables of orders 0 .. K, back to back: (4^(K+2) - 4) / 3"""
+    return (4 ** (K + 2) - 4) // 3
+
+
+def bg_model_order(counts, K, alpha, interpolate=True):
+    """float32 V of orders 0 .. K from their uint64 counters (pengk_bg_model_order, host only); alpha: K + 1 floats"""
+    n = np.ascontiguousarray(counts, np.uint64)
+    a = np.ascontiguousarray(alpha, np.float32)
+    assert not 0 <= K <= 5 or (len(n) >= order_table_size(K) and len(a) >= K + 1)
+    V = np.zeros(order_table_size(max(0, min(int(K), 5))), np.float32)
+    _check(lib().pengk_bg_model_order(n.ctypes.data, int(K), a.ctypes.data, int(bool(interpolate)), V.ctypes.data))
+    return V
 
 
 def match_quotas(h_in, h_ctrl, ratio=1):
@@ -776,6 +795,32 @@ class Context:
                                            scan[4] if n_seq is None else n_seq, _ptr(stratum), int(n_strata), int(W), _ptr(bg),
                                            _ptr(windows) if want_windows else None))
         return bg, windows
+
+    def bg_count_order(self, scan, K, all_valid=False, bg=None, n_seq=None):
+        """the (4^(K+2) - 4) / 3 background counters of orders 0 .. K of `scan`, on the device (pengk_bg_count_order).
+        all_valid: d_valid = NULL.  bg: a device uint64 array to ADD to instead of a fresh zeroed one.  n_seq: another
+        count than scan[4] (argument tests)."""
+        if bg is None:
+            bg = self.to_device(np.zeros(order_table_size(max(0, min(int(K), 5))), np.uint64))
+        _check(lib().pengk_bg_count_order(self.h, _ptr(scan[0]), None if all_valid else _ptr(scan[1]), _ptr(scan[2]), _ptr(scan[3]),
+                                          scan[4] if n_seq is None else n_seq, int(K), _ptr(bg)))
+        return bg
+
+    def pattern_stats_order(self, W, both, k, max_k, V, K, VK, ltot, counts, ctrl_counts=None, ctrl_ltot=None, pseudocount=0.0,
+                            bgprob=None, expected=None, logp=None, z=None):
+        """the sweep with an order-K model in its highest slot (pengk_pattern_stats_order).  V: device float32[84]; VK:
+        device float32, orders 0 .. K back to back; ctrl_counts / ctrl_ltot / pseudocount: the control of
+        pattern_stats_control, or none."""
+        n = 4 ** W
+        bgprob = bgprob if bgprob is not None else self.empty((max_k + 1, n), np.float32)
+        expected = expected if expected is not None else self.empty(n, np.float32)
+        logp = logp if logp is not None else self.empty(n, np.float32)
+        z = z if z is not None else self.empty(n, np.float32)
+        _check(lib().pengk_pattern_stats_order(self.h, W, int(both), k, max_k, _ptr(V), int(K), _ptr(VK), _ptr(ltot), _ptr(counts),
+                                               None if ctrl_counts is None else _ptr(ctrl_counts),
+                                               None if ctrl_ltot is None else _ptr(ctrl_ltot), float(pseudocount), _ptr(bgprob),
+                                               _ptr(expected), _ptr(logp), _ptr(z)))
+        return bgprob, expected, logp, z
 
     def iupac_aggregate(self, W, both, ids, counts, bgp, expected):
         ids = np.ascontiguousarray(ids, np.uint64)

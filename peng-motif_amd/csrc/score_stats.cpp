@@ -565,4 +565,33 @@ int pengk_dinuc_model(const uint64_t* h_counts1, const uint64_t* h_counts2, int 
   return PENGK_OK;
 }
 
+// BackgroundModel::calculateV (host/shared/BackgroundModel.cpp) continued to order K <= 5: float32, the same operations in
+// the same order (this file is compiled without fused multiply-adds).  DESIGN.md 29.
+int pengk_bg_model_order(const uint64_t* h_counts, int K, const float* h_alpha, int interpolate, float* h_V) {
+  if (!h_counts || !h_alpha || !h_V) return fail(PENGK_ERR_ARG, "pengk_bg_model_order: NULL argument");
+  if (K < 0 || K > 5) return fail(PENGK_ERR_ARG, "pengk_bg_model_order: order %d out of range [0,5]", K);
+  auto at = [](int k) { return (size_t)(((1u << (2 * (k + 1))) - 4u) / 3u); };
+  uint64_t base_counts = 0;
+  for (int y = 0; y < 4; ++y) base_counts += h_counts[y];
+  for (int y = 0; y < 4; ++y) h_V[y] = ((float)h_counts[y] + h_alpha[0] * 0.25f) / ((float)base_counts + h_alpha[0]);
+  for (int k = 1; k <= K; ++k) {
+    const int ny = 1 << (2 * (k + 1)), yk = 1 << (2 * k);
+    const uint64_t* n = h_counts + at(k);
+    const uint64_t* below = h_counts + at(k - 1);
+    float* v = h_V + at(k);
+    const float* prior_of = h_V + at(k - 1);
+    const float a = h_alpha[k];
+    for (int y = 0; y < ny; ++y) {
+      const float prior = interpolate ? prior_of[y % yk] : 0.25f;
+      v[y] = ((float)n[y] + a * prior) / ((float)below[y / 4] + a);
+    }
+    for (int g = 0; g < ny; g += 4) {
+      float factor = 0.0f;
+      for (int b = 0; b < 4; ++b) factor += v[g + b];
+      for (int b = 0; b < 4; ++b) v[g + b] /= factor;
+    }
+  }
+  return PENGK_OK;
+}
+
 }  // extern "C"

@@ -106,6 +106,9 @@ bool Global::stratifiedBackground = false;
 int Global::stratifiedGcBins = 10;
 unsigned long long Global::stratifiedMinBases = 10000;
 char* Global::stratifiedReportFilename = nullptr;
+int Global::highOrderBackground = 0;
+float Global::highOrderAlpha = 1.0f;
+char* Global::highOrderReportFilename = nullptr;
 bool Global::discriminative = false;
 double Global::discriminativePseudocount = 1.0;
 bool Global::scoreNegativesControl = false;
@@ -130,7 +133,7 @@ void Global::init(int nargs, char* args[]) {
   // enrichment scan the input after the motifs are found)
   pengk_host::keep_host_codes(scoreMotifs || sitesFilename || centralityFilename || refineFilename || spacingFilename ||
                               dinucFilename || enrichFilename || eraseFilename || maskLowComplexity || holdoutFilename ||
-                              dyadsFilename || positionalFilename || stratifiedBackground);
+                              dyadsFilename || positionalFilename || stratifiedBackground || highOrderBackground);
   // both strands are handled inside the count; sequences are always read single stranded
   // ... and every chunk of the input set is packed and sent to the device while the rest is still being read
   pengk_host::begin_streaming_pack(patternLength);
@@ -222,6 +225,7 @@ void Global::readArguments(int nargs, char* args[]) {
   const char* dyads_option = nullptr;  // ... with --dyads
   const char* positional_option = nullptr;  // ... with --positional
   const char* stratified_option = nullptr;  // ... with --stratified-background
+  const char* high_order_option = nullptr;  // ... with --high-order-background
   for (int i = 2; i < nargs; i++) {
     const char* a = args[i];
     if (!strcmp(a, "-w")) {
@@ -657,6 +661,30 @@ void Global::readArguments(int nargs, char* args[]) {
       if (bins) stratifiedGcBins = (int)n;
       else stratifiedMinBases = (unsigned long long)n;
       stratified_option = bins ? "--stratified-gc-bins" : "--stratified-min-bases";
+    } else if (!strcmp(a, "--high-order-background")) {
+      const char* v = need(i, nargs, args, printHelp);
+      char* end = nullptr;
+      const long n = std::strtol(v, &end, 10);
+      if (end == v || *end || n < 3 || n > 5) {
+        printHelp();
+        log_line("ERROR", "--high-order-background must be an integer in [3, 5]");
+        exit(4);
+      }
+      highOrderBackground = (int)n;
+    } else if (!strcmp(a, "--high-order-alpha")) {
+      const char* v = need(i, nargs, args, printHelp);
+      char* end = nullptr;
+      const double x = std::strtod(v, &end);
+      if (end == v || *end || !std::isfinite(x) || !(x > 0.0) || !((float)x > 0.0f) || !std::isfinite((float)x)) {
+        printHelp();
+        log_line("ERROR", "--high-order-alpha must be a finite number above 0");
+        exit(4);
+      }
+      highOrderAlpha = (float)x;
+      high_order_option = "--high-order-alpha";
+    } else if (!strcmp(a, "--high-order-report")) {
+      highOrderReportFilename = (char*)need(i, nargs, args, printHelp);
+      high_order_option = "--high-order-report";
     } else if (!strcmp(a, "--discriminative")) {
       discriminative = true;
     } else if (!strcmp(a, "--discriminative-pseudocount")) {
@@ -726,6 +754,22 @@ void Global::readArguments(int nargs, char* args[]) {
     printHelp();
     log_line("ERROR", std::string(stratified_option) + " requires --stratified-background");
     exit(4);
+  }
+  if (high_order_option && !highOrderBackground) {
+    printHelp();
+    log_line("ERROR", std::string(high_order_option) + " requires --high-order-background");
+    exit(4);
+  }
+  if (highOrderBackground) {
+    const char* why = nullptr;
+    if (highOrderBackground >= patternLength) why = "--high-order-background must be below the pattern length (-w)";
+    else if (stratifiedBackground) why = "--high-order-background cannot be combined with --stratified-background";
+    else if (bgModelOrder != 2 || maxOptBgModelOrder != 2) why = "--high-order-background needs the default --bg-model-order 2";
+    if (why) {
+      printHelp();
+      log_line("ERROR", why);
+      exit(4);
+    }
   }
   if (positional_option && !positionalFilename) {
     printHelp();
@@ -829,6 +873,15 @@ void Global::printHelp() {
   printf("  --stratified-min-bases INT     a bin whose model would be trained on fewer bases takes the global model (default 10000)\n");
   printf("  --stratified-report FILE       one line per bin, tab-separated: its GC range, sequences, windows, model bases,\n");
   printf("                                 the model used (own | global) and its four base probabilities\n");
+  printf("  --high-order-background K      score the k-mers against a Markov null of order K, 3..5 and below -w, in place of the\n");
+  printf("                                 order-2 model: counted on the device over the background set as it was read,\n");
+  printf("                                 interpolated like the lower orders.  For large inputs, where words built of common\n");
+  printf("                                 4-6-mers are enriched against an order-2 model.  A motif's own letters feed the\n");
+  printf("                                 model, so its z-score falls with K.  The reports' log-odds and p-values keep the one\n");
+  printf("                                 model; not with --stratified-background or another --bg-model-order than 2\n");
+  printf("  --high-order-alpha FLOAT       pseudo-count weight of orders 3..K, above 0 (default 1)\n");
+  printf("  --high-order-report FILE       one line per order 0..K, tab-separated: contexts, contexts seen, smallest and median\n");
+  printf("                                 count of a context\n");
   printf("  --erase FILE                   after the search, mask the sites of the motifs found and search what is left\n");
   printf("                                 again; the later rounds' motifs are appended.  FILE: one line per round and motif\n");
   printf("  --erase-rounds INT             further rounds of --erase, 1..8 (default 1); a round that finds or erases\n");

@@ -122,6 +122,9 @@ class Global {
   static int stratifiedGcBins;               // --stratified-gc-bins: 1..16
   static unsigned long long stratifiedMinBases;  // --stratified-min-bases: a stratum with fewer model bases takes the global model
   static char* stratifiedReportFilename;     // --stratified-report
+  static int highOrderBackground;            // --high-order-background K (new: an order 3..5 Markov null for the k-mer sweep); 0: off
+  static float highOrderAlpha;               // --high-order-alpha: the alpha of orders 3..K
+  static char* highOrderReportFilename;      // --high-order-report
   static bool discriminative;                // --discriminative (new: the k-mer sweep held to the control set's counts)
   static double discriminativePseudocount;   // --discriminative-pseudocount
   static bool scoreNegativesControl;         // --score-negatives control (new: the --background-sequences file as negatives, matched to the input)

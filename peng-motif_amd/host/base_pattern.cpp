@@ -15,6 +15,7 @@
 #include <iostream>
 
 #include "Global.h"
+#include "motif_bg_order.h"
 #include "motif_strata.h"
 #include "ranked_prefix.h"
 #include "utils.h"
@@ -132,6 +133,7 @@ BasePattern::BasePattern(const size_t pattern_length, Strand s, const int k, con
   // --stratified-background: the mixture of the GC strata's models in place of the one model, the control's share on top
   // of it under --discriminative; d_V still holds the one model, which the dump below leaves as V.f32
   const StratifiedNull* strata = pengk_host::stratified_null();
+  const HighOrderNull* order = pengk_host::high_order_null();
   if (strata) {
     pengk_host::DeviceBuffer<float> d_strata_V(strata->V.size());
     d_strata_V.upload(strata->V.data(), strata->V.size());
@@ -142,6 +144,18 @@ BasePattern::BasePattern(const size_t pattern_length, Strand s, const int k, con
                                      d_logp.get(), d_z.get()),
           "pengk_pattern_stats_strata");
     check(pengk_synchronize(context()), "pengk_synchronize");  // (the strata's tables leave scope here)
+  } else if (order) {
+    // --high-order-background: the order-K model's probabilities in the slot of the run's order (k = max_k = 2), the
+    // control's share on top of them under --discriminative; V.f32 below stays the one model
+    pengk_host::DeviceBuffer<float> d_order_V(order->V.size());
+    d_order_V.upload(order->V.data(), order->V.size());
+    check(pengk_pattern_stats_order(context(), W, both, this->k, this->max_k, d_V.get(), order->K, d_order_V.get(), d_ltot.get(),
+                                    d_counts.get(), discriminative ? d_ctrl_counts.get() : nullptr,
+                                    discriminative ? d_ctrl_ltot.get() : nullptr,
+                                    discriminative ? Global::discriminativePseudocount : 0.0, d_bgprob.get(), d_expected.get(),
+                                    d_logp.get(), d_z.get()),
+          "pengk_pattern_stats_order");
+    check(pengk_synchronize(context()), "pengk_synchronize");  // (the model's tables leave scope here)
   } else if (discriminative)
     check(pengk_pattern_stats_control(context(), W, both, this->k, this->max_k, d_V.get(), d_ltot.get(), d_counts.get(),
                                       d_ctrl_counts.get(), d_ctrl_ltot.get(), Global::discriminativePseudocount, d_bgprob.get(),
@@ -188,6 +202,10 @@ BasePattern::BasePattern(const size_t pattern_length, Strand s, const int k, con
         meta += "strata " + std::to_string(strata->G);
         for (uint64_t w : strata->windows) meta += " " + std::to_string(w);
         meta += "\n";
+      }
+      if (order) {
+        dump("order_V.f32", order->V.data(), order->V.size() * sizeof(float));
+        meta += "order " + std::to_string(order->K) + "\n";
       }
       dump("meta.txt", meta.data(), meta.size());
     }

@@ -24,6 +24,7 @@
 #include "motif_holdout.h"
 #include "motif_match.h"
 #include "motif_positional.h"
+#include "motif_bg_order.h"
 #include "motif_strata.h"
 #include "motif_refine.h"
 #include "motif_spacing.h"
@@ -183,6 +184,24 @@ int main(int nargs, char** args) {
     pengk_host::set_stratified_null(&stratified);
     clock.lap("stratified background");
   }
+  // --high-order-background: the sweep's null becomes a Markov model of order 3 .. 5 of the background set as it was read
+  // -- no mask, no hold-out, like the one model above; the rounds of --erase keep it
+  HighOrderNull high_order;
+  if (Global::highOrderBackground && Global::patternLength >= PENGK_MIN_W && Global::patternLength <= PENGK_MAX_W &&
+      Global::patternLength % 2 == 0) {
+    if (!scan) {
+      scan.reset(new ScanInput);
+      build_scan_input(*Global::inputSequenceSet, scan.get());
+    }
+    HighOrderSettings hs;
+    hs.order = Global::highOrderBackground;
+    hs.alpha = Global::highOrderAlpha;
+    hs.report_path = Global::highOrderReportFilename;
+    build_high_order_null(*scan, Global::backgroundSequenceSet != Global::inputSequenceSet ? Global::backgroundSequenceSet : nullptr, hs,
+                          &high_order);
+    pengk_host::set_high_order_null(&high_order);
+    clock.lap("high-order background");
+  }
   Peng peng(Global::strand, Global::bgModelOrder, Global::maxOptBgModelOrder, Global::inputSequenceSet, bgModel);
 
   PengParameters params;
@@ -230,6 +249,7 @@ int main(int nargs, char** args) {
   }
   if (lc_mask.control_attached || holdout.control_attached) pengk_host::override_control_input(nullptr, nullptr);
   pengk_host::set_stratified_null(nullptr);
+  pengk_host::set_high_order_null(nullptr);
   if (holdout.attached) pengk_host::override_sequence_count(nullptr, 0);
   // (--enrich scores against the negatives of --score-motifs and --dinuc: with it they are built once, for all three)
   // (--score-negatives control: the control set, matched to the input, serves whichever of the three is asked for)
