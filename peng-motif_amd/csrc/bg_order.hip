@@ -1,9 +1,8 @@
 // bg_order.hip -- the background counters of orders 0 .. K <= 5 of a scan layout (pengk_bg_count_order,
 // --high-order-background): (4^(K+2) - 4) / 3 (k+1)-mer counters in one pass over the words.
 //
-//   tile     64 consecutive positions of one sequence, one wave, one position per lane, as strata.hip reads them: the 16
-//            bases from q = max(p - 5, 0) on (two 32-bit halves of the layout's words, one funnel shift) and the 32
-//            validity bits from q on.
+//   tile     64 consecutive positions of one sequence, one wave, one position per lane: the window of tile_walk.h with
+//            five bases behind the position, 16 bases and 32 validity bits from q = max(p - 5, 0) on.
 //   longest  a position with a valid base sends ONE LDS atomic: to the table of its longest available order
 //            m = min(K, valid bases right behind it, p), at the (m+1)-mer ending at p in BaMM order.  (strata.hip's ballots
 //            stop at 64 keys; order 5 has 4096.)  Lanes that hold the key of the wave's first counting lane -- all of them
@@ -17,6 +16,7 @@
 // d_bg is ADDED to; nothing else is written.
 #include "pengk_internal.h"
 #include "scan_walk.h"
+#include "tile_walk.h"
 
 namespace pengk {
 namespace {
@@ -28,15 +28,6 @@ constexpr uint32_t BGO_FLUSH_TILES = 1u << 25;                     // x 64 posit
 constexpr uint32_t BGO_CHUNK_TILES = BGO_FLUSH_TILES / BGO_WAVES;  // a round: at most BGO_FLUSH_TILES tiles over the waves
 constexpr int BGO_PER_CU = 4;                                      // workgroups a CU: 32 waves, 87 KB of LDS at K = 5
 
-__host__ __device__ constexpr uint32_t bgo_at(int k) { return ((1u << (2 * (k + 1))) - 4u) / 3u; }  // 0, 4, 20, 84, 340, 1364, 5460
-static_assert(bgo_at(BGO_MAX_K + 1) == 5460u && bgo_at(3) == 84u, "the tables' places");
-
-__device__ __forceinline__ uint32_t bgo_valid_word(const uint32_t* vp, uint32_t L, uint32_t nw, uint32_t j) {
-  if (j >= nw) return 0u;
-  const uint32_t rem = L - 32u * j;
-  const uint32_t in = rem >= 32u ? 0xFFFFFFFFu : ((1u << rem) - 1u);
-  return vp ? vp[j] & in : in;
-}
 
 // the 16 two-bit digits of e in reverse order
 __device__ __forceinline__ uint32_t bgo_reverse_digits(uint32_t e) {
@@ -49,12 +40,12 @@ __device__ __forceinline__ uint32_t bgo_reverse_digits(uint32_t e) {
 __device__ __forceinline__ void bgo_flush(uint32_t* sh, int K, unsigned long long* __restrict__ bg) {
   __syncthreads();
   for (int k = K - 1; k >= 0; --k) {
-    const uint32_t ny = 1u << (2 * (k + 1)), at = bgo_at(k), up = bgo_at(k + 1);
+    const uint32_t ny = 1u << (2 * (k + 1)), at = order_table_at(k), up = order_table_at(k + 1);
     for (uint32_t y = threadIdx.x; y < ny; y += BGO_THREADS)
       sh[at + y] += sh[up + y] + sh[up + ny + y] + sh[up + 2u * ny + y] + sh[up + 3u * ny + y];
     __syncthreads();
   }
-  const uint32_t total = bgo_at(K + 1);
+  const uint32_t total = order_table_at(K + 1);
   for (uint32_t q = threadIdx.x; q < total; q += BGO_THREADS) {
     const uint32_t c = sh[q];
     if (!c) continue;
@@ -67,8 +58,8 @@ __device__ __forceinline__ void bgo_flush(uint32_t* sh, int K, unsigned long lon
 __global__ __launch_bounds__(BGO_THREADS) void bg_order_kernel(const uint64_t* __restrict__ words, const uint32_t* __restrict__ valid,
                                                                const int64_t* __restrict__ offs, const uint32_t* __restrict__ lens,
                                                                uint64_t n_seq, int K, unsigned long long* __restrict__ bg) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t sh[];  // bgo_at(K + 1) counters
-  const uint32_t total = bgo_at(K + 1);
+  extern __shared__ __attribute__((aligned(16))) uint32_t sh[];  // order_table_at(K + 1) counters
+  const uint32_t total = order_table_at(K + 1);
   for (uint32_t q = threadIdx.x; q < total; q += BGO_THREADS) sh[q] = 0u;
   __syncthreads();
   const uint32_t lane = threadIdx.x & 63u;
@@ -92,8 +83,6 @@ __global__ __launch_bounds__(BGO_THREADS) void bg_order_kernel(const uint64_t* _
     const uint64_t w0 = L ? (uint64_t)offs[i] >> 5 : 0ull;
     const uint64_t* wp = words + w0;
     const uint32_t* vp = valid ? valid + w0 : nullptr;
-    const uint32_t* hp = reinterpret_cast<const uint32_t*>(wp);
-    const uint32_t nh = (L + 15u) >> 4, nw = (L + 31u) >> 5;
     for (uint32_t t0 = 0; t0 < most; t0 += BGO_CHUNK_TILES) {  // (one chunk but for sequences beyond 2^28 bases)
       const uint32_t left = most - t0;
       const uint32_t round_tiles = (left < BGO_CHUNK_TILES ? left : BGO_CHUNK_TILES) * (uint32_t)BGO_WAVES;  // (an upper bound, <= BGO_FLUSH_TILES)
@@ -105,14 +94,8 @@ __global__ __launch_bounds__(BGO_THREADS) void bg_order_kernel(const uint64_t* _
       const uint32_t t1 = t0 + BGO_CHUNK_TILES < n_tiles ? t0 + BGO_CHUNK_TILES : n_tiles;
       for (uint32_t t = t0; t < t1; ++t) {
         const uint32_t p = (t << 6) + lane;
-        const uint32_t q = p >= (uint32_t)BGO_MAX_K ? p - (uint32_t)BGO_MAX_K : 0u;
-        const uint32_t off = p - q;  // the lane's own place in its window: 5 but at the sequence's start
-        const uint32_t h = q >> 4;
-        const uint32_t H0 = h < nh ? hp[h] : 0u, H1 = h + 1u < nh ? hp[h + 1u] : 0u;
-        const uint32_t lo = __builtin_amdgcn_alignbit(H1, H0, (q & 15u) << 1);  // the 16 bases from q on
-        const uint32_t j = q >> 5;
-        const uint32_t V0 = bgo_valid_word(vp, L, nw, j), V1 = bgo_valid_word(vp, L, nw, j + 1u);
-        const uint32_t v = __builtin_amdgcn_alignbit(V1, V0, q & 31u);  // the validity bits of the 32 bases from q on
+        const tile::Window w = tile::window(wp, vp, L, p, (uint32_t)BGO_MAX_K);
+        const uint32_t lo = w.lo, v = w.v, off = w.off;  // (off: 5 but at the sequence's start)
         const bool ok = (v >> off) & 1u;  // (beyond the sequence's end: no bit)
         // valid bases from p downwards, p included: what lies before q is shifted in as zero, so the run ends at the
         // sequence's start as well
@@ -121,7 +104,7 @@ __global__ __launch_bounds__(BGO_THREADS) void bg_order_kernel(const uint64_t* _
         // the (m+1)-mer ending at p, older base more significant: the window's digits off - m .. off, reversed
         const uint32_t e = (lo >> (2u * (off - m))) & ((1u << (2u * (m + 1u))) - 1u);
         const uint32_t y = bgo_reverse_digits(e) >> (32u - 2u * (m + 1u));
-        const uint32_t idx = ((1u << (2u * (m + 1u))) - 4u) / 3u + y;  // (< bgo_at(K + 1): m <= K, y < 4^(m+1))
+        const uint32_t idx = order_table_at((int)m) + y;  // (< order_table_at(K + 1): m <= K, y < 4^(m+1))
         const unsigned long long counting = __ballot(ok);
         if (counting == 0ull) continue;
         const uint32_t lead = (uint32_t)__ffsll((long long)counting) - 1u;  // the first lane that counts, and those with its key
@@ -152,7 +135,7 @@ int pengk_bg_count_order(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t
   int rc = enter(ctx);
   if (rc) return rc;
   if (n_seq == 0) return PENGK_OK;
-  const size_t lds = (size_t)bgo_at(K + 1) * sizeof(uint32_t);
+  const size_t lds = (size_t)order_table_at(K + 1) * sizeof(uint32_t);
   const int grid = grid_for(ctx, n_seq, BGO_WAVES, BGO_PER_CU);
   hipLaunchKernelGGL(bg_order_kernel, dim3(grid), dim3(BGO_THREADS), lds, ctx->stream, d_words, d_valid, d_offs, d_lens, n_seq, K,
                      (unsigned long long*)d_bg);

@@ -11,15 +11,17 @@
 //            one word) at the lane's last slot.  No table of triplet counters, no LDS array, no barrier.
 //   cover    end(i) = i + lmax(i) + 2; base b is covered iff the running maximum of end over the starts <= b exceeds b
 //            (a wave prefix maximum: six shuffles).
-//   tiles    tile counts per sequence -> exclusive sums (two small launches), then every wave of a fixed grid takes one
-//            contiguous share of the tiles: a binary search for its first tile, then a walk.  Static: nothing is handed
-//            out at run time.
+//   tiles    tile counts per sequence -> exclusive sums (the plan of tile_walk.h), then every wave of a fixed grid takes
+//            one contiguous share of the tiles: a binary search for its first tile, then a walk.  Static: nothing is
+//            handed out at run time.  The walk is written out here and not tile_walk.h's cursor: under the cursor this
+//            kernel measured 1.7 % slower (profiles/tile_walk_probe.log), though its step loop compiles the same.
 // What lies beyond the right halo is wrong by construction and flows only into starts whose results are not used:
 // (i, l) reads (i+1, l-1) and nothing else of another start.  Registers only: no address depends on such a value.
 #include <algorithm>
 
 #include "pengk_internal.h"
 #include "scan_walk.h"
+#include "tile_walk.h"
 
 namespace pengk {
 namespace {
@@ -42,61 +44,14 @@ __host__ __device__ __forceinline__ uint32_t dust_tiles(uint32_t L) {
   return 2u + ((L > two ? L - two : 0u) + DUST_STEP - 1u) / DUST_STEP;
 }
 
-__device__ __forceinline__ uint32_t dust_valid_word(const uint32_t* vp, uint32_t L, uint32_t nw, uint32_t j) {
-  if (j >= nw) return 0u;
-  const uint32_t rem = L - 32u * j;
-  const uint32_t in = rem >= 32u ? 0xFFFFFFFFu : ((1u << rem) - 1u);
-  return vp ? vp[j] & in : in;
-}
-
-// ---- tile counts and their exclusive sums -----------------------------------------------------------------------------
-__device__ __forceinline__ unsigned long long dust_group_inclusive_sum(unsigned long long v, unsigned long long* sh) {
-  const int t = threadIdx.x;
-  sh[t] = v;
-  __syncthreads();
-  for (int d = 1; d < DUST_THREADS; d <<= 1) {
-    const unsigned long long x = t >= d ? sh[t - d] : 0ull;
-    __syncthreads();
-    sh[t] += x;
-    __syncthreads();
-  }
-  const unsigned long long r = sh[t];
-  __syncthreads();
-  return r;
-}
-
-// excl[i]: the tiles of the sequences in front of i within its group of 256; boff[b]: the tiles of group b; flag[i] = 0
-__global__ __launch_bounds__(DUST_THREADS) void dust_tiles_kernel(const uint32_t* __restrict__ lens, uint64_t n_seq,
-                                                                  unsigned long long* __restrict__ excl,
-                                                                  unsigned long long* __restrict__ boff,
-                                                                  uint32_t* __restrict__ flag) {
-  __shared__ unsigned long long sh[DUST_THREADS];
-  const uint64_t i = (uint64_t)blockIdx.x * DUST_THREADS + threadIdx.x;
-  const unsigned long long nt = i < n_seq ? dust_tiles(lens[i]) : 0u;
-  const unsigned long long incl = dust_group_inclusive_sum(nt, sh);
-  if (i < n_seq) {
-    excl[i] = incl - nt;
-    flag[i] = 0u;
-  }
-  if (threadIdx.x == DUST_THREADS - 1) boff[blockIdx.x] = incl;
-}
-
-// boff[0 .. n_groups) -> exclusive sums in place, boff[n_groups] = the total; one workgroup
-__global__ __launch_bounds__(DUST_THREADS) void dust_groups_kernel(unsigned long long* __restrict__ boff, uint64_t n_groups) {
-  __shared__ unsigned long long sh[DUST_THREADS];
-  unsigned long long carry = 0;
-  for (uint64_t b = 0; b < n_groups; b += DUST_THREADS) {
-    const uint64_t k = b + threadIdx.x;
-    const unsigned long long v = k < n_groups ? boff[k] : 0ull;
-    const unsigned long long incl = dust_group_inclusive_sum(v, sh);
-    if (k < n_groups) boff[k] = carry + incl - v;
-    sh[threadIdx.x] = incl;  // (the last thread's is the chunk's total)
-    __syncthreads();
-    carry += sh[DUST_THREADS - 1];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) boff[n_groups] = carry;
-}
+struct DustTilesOf {
+  __device__ __forceinline__ tile::Tiles operator()(uint32_t L) const { return tile::Tiles{dust_tiles(L)}; }
+};
+// beside the tile counts: flag[i] = 0
+struct DustClearFlag {
+  uint32_t* flag;
+  __device__ __forceinline__ void operator()(uint64_t i) const { flag[i] = 0u; }
+};
 
 // ---- the mask ---------------------------------------------------------------------------------------------------------
 // One tile: the bases [s0, s0 + 256) of a sequence of L bases whose words / validity words begin at wp / vp (vp NULL:
@@ -117,7 +72,7 @@ __device__ __forceinline__ uint32_t dust_tile(const uint64_t* __restrict__ wp, c
   for (int q = 0; q < 3; ++q) {
     const bool in = k0 + q < nw;
     W[q] = in ? wp[k0 + q] : 0ull;
-    V[q] = in ? dust_valid_word(vp, L, nw, (uint32_t)(k0 + q)) : 0u;
+    V[q] = in ? tile::valid_word(vp, L, nw, (uint32_t)(k0 + q)) : 0u;
   }
   uint64_t A0 = W[0], A1 = W[1], A2 = W[2];
   const uint64_t vlo = (uint64_t)V[0] | ((uint64_t)V[1] << 32);
@@ -199,7 +154,7 @@ __device__ __forceinline__ uint32_t dust_tile(const uint64_t* __restrict__ wp, c
   uint32_t cleared = 0u;
   const uint64_t kw = (s0 >> 5) + (lane >> 3);  // the sequence's word this lane group holds
   if ((lane & 7u) == 0u && 32ull * kw >= o0 && 32ull * kw < o1) {
-    const uint32_t in = dust_valid_word(vp, L, nw, (uint32_t)kw);
+    const uint32_t in = tile::valid_word(vp, L, nw, (uint32_t)kw);
     op[kw] = in & ~word;
     cleared = (uint32_t)__popc(in & word);
   }
@@ -217,7 +172,7 @@ __global__ __launch_bounds__(DUST_THREADS) void dust_mask_kernel(const uint64_t*
   __shared__ unsigned long long bsum;
   if (threadIdx.x == 0) bsum = 0;
   __syncthreads();
-  // this wave's share of the tiles: [g, g1)
+  // this wave's share of the tiles: [g, g1) (what tile::share and tile::Cursor do, written out: see the header comment)
   const uint64_t total = boff[n_groups];
   const uint64_t n_waves = (uint64_t)gridDim.x * DUST_WAVES;
   const uint64_t wave = (uint64_t)blockIdx.x * DUST_WAVES + (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -234,7 +189,7 @@ __global__ __launch_bounds__(DUST_THREADS) void dust_mask_kernel(const uint64_t*
       else hi = mid;
     }
     const uint64_t rest = g - boff[lo];
-    uint64_t i = lo * DUST_THREADS, ihi = std::min<uint64_t>(n_seq, i + DUST_THREADS);
+    uint64_t i = lo * tile::PLAN_THREADS, ihi = std::min<uint64_t>(n_seq, i + tile::PLAN_THREADS);
     while (ihi - i > 1) {
       const uint64_t mid = i + (ihi - i) / 2;
       if (excl[mid] <= rest) i = mid;
@@ -300,18 +255,14 @@ int pengk_mask_low_complexity(pengk_ctx* ctx, const uint64_t* d_words, const uin
   int rc = enter(ctx);
   if (rc) return rc;
   if (n_seq == 0) return PENGK_OK;
-  const uint64_t n_groups = (n_seq + DUST_THREADS - 1) / DUST_THREADS;
-  // scratch: excl (n_seq uint64) | boff (n_groups + 1 uint64) | flag (n_seq uint32)
-  rc = ensure_scratch(ctx, &ctx->d_sites, &ctx->sites_bytes, (n_seq + n_groups + 1) * sizeof(uint64_t) + n_seq * sizeof(uint32_t));
+  // scratch: excl | boff (tile_walk.h) | flag (n_seq uint32)
+  rc = ensure_scratch(ctx, &ctx->d_sites, &ctx->sites_bytes, tile::plan_bytes(n_seq) + n_seq * sizeof(uint32_t));
   if (rc) return rc;
-  unsigned long long* excl = (unsigned long long*)ctx->d_sites;
-  unsigned long long* boff = excl + n_seq;
-  uint32_t* flag = (uint32_t*)(boff + n_groups + 1);
+  uint32_t* flag = (uint32_t*)((char*)ctx->d_sites + tile::plan_bytes(n_seq));
   unsigned long long* masked = (unsigned long long*)d_masked;
-  hipLaunchKernelGGL(dust_tiles_kernel, dim3((unsigned)n_groups), dim3(DUST_THREADS), 0, ctx->stream, d_lens, n_seq, excl, boff, flag);
-  hipLaunchKernelGGL(dust_groups_kernel, dim3(1), dim3(DUST_THREADS), 0, ctx->stream, boff, n_groups);
+  const tile::Plan plan = tile::plan(ctx, ctx->d_sites, d_lens, n_seq, DustTilesOf{}, DustClearFlag{flag});
   hipLaunchKernelGGL(dust_mask_kernel, dim3((unsigned)ctx->num_cu * 8u), dim3(DUST_THREADS), 0, ctx->stream, d_words, d_valid, d_offs,
-                     d_lens, n_seq, (uint32_t)threshold, excl, boff, n_groups, flag, d_out_valid, masked);
+                     d_lens, n_seq, (uint32_t)threshold, plan.excl, plan.boff, plan.n_groups, flag, d_out_valid, masked);
   hipLaunchKernelGGL(dust_touched_kernel, dim3(grid_for(ctx, n_seq, DUST_THREADS, 16)), dim3(DUST_THREADS), 0, ctx->stream, flag,
                      n_seq, masked + 1);
   PENGK_HIP(hipGetLastError());

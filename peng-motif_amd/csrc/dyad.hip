@@ -15,10 +15,9 @@
 //            flush turns a bin's code into the public key (first base highest), folds it again in that order -- a pair
 //            {code, its reverse complement} is one bin here and one there -- and adds the bin to the uint64 table with a
 //            plain vector atomic; empty bins add nothing, so no entry that is not canonical is ever written.
-//   tiles    tile counts per sequence -> exclusive sums (two small launches), then every wave of a fixed grid takes one
-//            contiguous share of the tiles: a binary search for its first tile, then a walk.  Static: nothing is handed
-//            out at run time, and every wave of the grid runs the same number of rounds, so the barriers of the flush sit
-//            in workgroup-uniform control flow.
+//   tiles    tile counts per sequence -> exclusive sums, then every wave of a fixed grid walks one contiguous share of
+//            the tiles: the plan, the share and the cursor of tile_walk.h.  Every wave of the grid runs the same number
+//            of rounds, so the barriers of the flush sit in workgroup-uniform control flow.
 //   wrap     a position bumps a bin at most once, a round of a workgroup holds at most 1024 positions, and the tables are
 //            flushed every DYAD_FLUSH_ROUNDS = 2^21 rounds: no bin exceeds 2^31 between two flushes.
 // Nothing of size positions x gaps is written to HBM.
@@ -27,6 +26,7 @@
 #include <vector>
 
 #include "pengk_internal.h"
+#include "tile_walk.h"
 
 namespace pengk {
 namespace {
@@ -36,63 +36,14 @@ constexpr int DYAD_WAVES = DYAD_THREADS / 64;
 constexpr int DYAD_GROUP = 8;                     // gaps a workgroup holds at most
 constexpr int DYAD_BINS = 4096;
 constexpr uint32_t DYAD_FLUSH_ROUNDS = 1u << 21;  // x 1024 positions a round = 2^31 per bin at most
-constexpr int DYAD_SCAN_THREADS = 256;
 static_assert(6 + PENGK_DYAD_MAX_GAP == 32, "a position's span lies in its word and the next");
 static_assert(DYAD_GROUP * DYAD_BINS * 4 + 256 <= 160 * 1024, "a group's tables and the triplets fit in LDS");
 
 __host__ __device__ __forceinline__ uint32_t dyad_tiles(uint32_t L) { return L < 3u ? 0u : ((L - 3u) >> 6) + 1u; }
 
-__device__ __forceinline__ uint32_t dyad_valid_word(const uint32_t* vp, uint32_t L, uint32_t nw, uint32_t j) {
-  if (j >= nw) return 0u;
-  const uint32_t rem = L - 32u * j;
-  const uint32_t in = rem >= 32u ? 0xFFFFFFFFu : ((1u << rem) - 1u);
-  return vp ? vp[j] & in : in;
-}
-
-// ---- tile counts and their exclusive sums (the scheme of dust.hip) ------------------------------------------------------
-__device__ __forceinline__ unsigned long long dyad_group_inclusive_sum(unsigned long long v, unsigned long long* sh) {
-  const int t = threadIdx.x;
-  sh[t] = v;
-  __syncthreads();
-  for (int d = 1; d < DYAD_SCAN_THREADS; d <<= 1) {
-    const unsigned long long x = t >= d ? sh[t - d] : 0ull;
-    __syncthreads();
-    sh[t] += x;
-    __syncthreads();
-  }
-  const unsigned long long r = sh[t];
-  __syncthreads();
-  return r;
-}
-
-// excl[i]: the tiles of the sequences in front of i within its group of 256; boff[b]: the tiles of group b
-__global__ __launch_bounds__(DYAD_SCAN_THREADS) void dyad_tiles_kernel(const uint32_t* __restrict__ lens, uint64_t n_seq,
-                                                                       unsigned long long* __restrict__ excl,
-                                                                       unsigned long long* __restrict__ boff) {
-  __shared__ unsigned long long sh[DYAD_SCAN_THREADS];
-  const uint64_t i = (uint64_t)blockIdx.x * DYAD_SCAN_THREADS + threadIdx.x;
-  const unsigned long long nt = i < n_seq ? dyad_tiles(lens[i]) : 0u;
-  const unsigned long long incl = dyad_group_inclusive_sum(nt, sh);
-  if (i < n_seq) excl[i] = incl - nt;
-  if (threadIdx.x == DYAD_SCAN_THREADS - 1) boff[blockIdx.x] = incl;
-}
-
-// boff[0 .. n_groups) -> exclusive sums in place, boff[n_groups] = the total; one workgroup
-__global__ __launch_bounds__(DYAD_SCAN_THREADS) void dyad_groups_kernel(unsigned long long* __restrict__ boff, uint64_t n_groups) {
-  __shared__ unsigned long long sh[DYAD_SCAN_THREADS];
-  unsigned long long carry = 0;
-  for (uint64_t b = 0; b < n_groups; b += DYAD_SCAN_THREADS) {
-    const uint64_t k = b + threadIdx.x;
-    const unsigned long long v = k < n_groups ? boff[k] : 0ull;
-    const unsigned long long incl = dyad_group_inclusive_sum(v, sh);
-    if (k < n_groups) boff[k] = carry + incl - v;
-    sh[threadIdx.x] = incl;  // (the last thread's is the chunk's total)
-    __syncthreads();
-    carry += sh[DYAD_SCAN_THREADS - 1];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) boff[n_groups] = carry;
-}
+struct DyadTilesOf {
+  __device__ __forceinline__ tile::Tiles operator()(uint32_t L) const { return tile::Tiles{dyad_tiles(L)}; }
+};
 
 // ---- the count ----------------------------------------------------------------------------------------------------------
 // the reverse complement of 32 bases (first base lowest): the digits complemented and in reverse order
@@ -114,7 +65,7 @@ __device__ __forceinline__ void dyad_tile(const uint64_t* __restrict__ wp, const
   const uint32_t j = 2u * k + (lane >> 5);  // the word of this lane's position (k < 2^26)
   const uint32_t s = lane & 31u;            // ... and its place in it
   const uint64_t W0 = j < nw ? wp[j] : 0ull, W1 = j + 1u < nw ? wp[j + 1u] : 0ull;
-  const uint32_t V0 = dyad_valid_word(vp, L, nw, j), V1 = dyad_valid_word(vp, L, nw, j + 1u);
+  const uint32_t V0 = tile::valid_word(vp, L, nw, j), V1 = tile::valid_word(vp, L, nw, j + 1u);
   const uint64_t x = s ? (W0 >> (2u * s)) | (W1 << (64u - 2u * s)) : W0;  // the 32 bases from the position on
   const uint32_t v = s ? (V0 >> s) | (V1 << (32u - s)) : V0;              // ... and their validity bits
   const uint32_t r = v == 0xFFFFFFFFu ? 32u : (uint32_t)__builtin_ctz(~v);
@@ -187,52 +138,22 @@ __global__ __launch_bounds__(DYAD_THREADS) void dyad_count_kernel(const uint64_t
   uint32_t* bins = sh;
   uint32_t* mono = sh + ng * DYAD_BINS;
   const bool with_mono = blockIdx.y == 0;
-  // this wave's share of the tiles: [g, gend); `per` rounds for every wave of the grid
-  const uint64_t total = boff[n_groups];
-  const uint64_t n_waves = (uint64_t)gridDim.x * DYAD_WAVES;
-  const uint64_t per = (total + n_waves - 1) / n_waves;
-  if ((uint64_t)blockIdx.x * DYAD_WAVES * per >= total) return;  // (the whole workgroup: nothing to zero, nothing to flush)
+  // this wave's share of the tiles; `per` rounds for every wave of the grid
+  const tile::Share share = tile::share<DYAD_WAVES>(boff, n_groups);
+  if (share.block_empty) return;  // (the whole workgroup: nothing to zero, nothing to flush)
   for (int q = threadIdx.x; q < ng * DYAD_BINS + 64; q += DYAD_THREADS) sh[q] = 0u;
   __syncthreads();
-  const uint64_t wave = (uint64_t)blockIdx.x * DYAD_WAVES + (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  uint64_t g = wave * per;
-  const uint64_t gend = g + per < total ? g + per : total;
-  uint64_t i = 0;
-  uint32_t k = 0, L = 0, nt = 0;
-  if (g < gend) {
-    // the sequence and the tile of it that g is: the last group with boff <= g, the last sequence of it with excl <= rest
-    uint64_t lo = 0, hi = n_groups;  // boff[lo] <= g < boff[hi]
-    while (hi - lo > 1) {
-      const uint64_t mid = lo + (hi - lo) / 2;
-      if (boff[mid] <= g) lo = mid;
-      else hi = mid;
-    }
-    const uint64_t rest = g - boff[lo];
-    i = lo * DYAD_SCAN_THREADS;
-    uint64_t ihi = std::min<uint64_t>(n_seq, i + DYAD_SCAN_THREADS);
-    while (ihi - i > 1) {
-      const uint64_t mid = i + (ihi - i) / 2;
-      if (excl[mid] <= rest) i = mid;
-      else ihi = mid;
-    }
-    k = (uint32_t)(rest - excl[i]);
-    L = lens[i];
-    nt = dyad_tiles(L);
-  }
+  uint64_t g = share.g;
+  tile::Cursor<DyadTilesOf> c{lens, n_seq, DyadTilesOf{}};
+  if (g < share.gend) c.locate(g, excl, boff, n_groups);
   uint32_t since = 0;
-  for (uint64_t round = 0; round < per; ++round) {  // (per, and so every barrier below, is the same for the whole grid)
-    if (g < gend) {
-      while (k >= nt) {  // the next sequence that has a tile (there is one: g < total)
-        if (++i >= n_seq) break;
-        L = lens[i];
-        nt = dyad_tiles(L);
-        k = 0;
+  for (uint64_t round = 0; round < share.per; ++round) {  // (per, and so every barrier below, is the same for the whole grid)
+    if (g < share.gend) {
+      if (c.next()) {
+        const uint64_t w0 = (uint64_t)offs[c.i] >> 5;
+        dyad_tile<BOTH>(words + w0, valid ? valid + w0 : nullptr, c.L, c.k, g0, g1, bins, with_mono ? mono : nullptr);
       }
-      if (i < n_seq) {
-        const uint64_t w0 = (uint64_t)offs[i] >> 5;
-        dyad_tile<BOTH>(words + w0, valid ? valid + w0 : nullptr, L, k, g0, g1, bins, with_mono ? mono : nullptr);
-      }
-      ++k;
+      ++c.k;
       ++g;
     }
     if (++since == DYAD_FLUSH_ROUNDS) {
@@ -261,12 +182,8 @@ int pengk_dyad_count(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_
   int rc = enter(ctx);
   if (rc) return rc;
   if (n_seq == 0) return PENGK_OK;
-  const uint64_t n_groups = (n_seq + DYAD_SCAN_THREADS - 1) / DYAD_SCAN_THREADS;
-  // scratch: excl (n_seq uint64) | boff (n_groups + 1 uint64)
-  rc = ensure_scratch(ctx, &ctx->d_sites, &ctx->sites_bytes, (n_seq + n_groups + 1) * sizeof(uint64_t));
+  rc = ensure_scratch(ctx, &ctx->d_sites, &ctx->sites_bytes, tile::plan_bytes(n_seq));
   if (rc) return rc;
-  unsigned long long* excl = (unsigned long long*)ctx->d_sites;
-  unsigned long long* boff = excl + n_seq;
   // the gaps in equal groups of at most DYAD_GROUP: 21 gaps are 3 x 7, 27 are 4 x 7
   const int n_gaps = max_gap + 1;
   const int gap_groups = (n_gaps + DYAD_GROUP - 1) / DYAD_GROUP;
@@ -274,16 +191,15 @@ int pengk_dyad_count(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_
   const size_t lds = (size_t)per_group * DYAD_BINS * sizeof(uint32_t) + 64 * sizeof(uint32_t);
   const unsigned per_cu = lds * 2 <= 160 * 1024 ? 2u : 1u;  // (32 waves a CU: two workgroups of 1024 threads at most)
   const dim3 grid((unsigned)ctx->num_cu * per_cu, (unsigned)gap_groups);
-  hipLaunchKernelGGL(dyad_tiles_kernel, dim3((unsigned)n_groups), dim3(DYAD_SCAN_THREADS), 0, ctx->stream, d_lens, n_seq, excl, boff);
-  hipLaunchKernelGGL(dyad_groups_kernel, dim3(1), dim3(DYAD_SCAN_THREADS), 0, ctx->stream, boff, n_groups);
+  const tile::Plan plan = tile::plan(ctx, ctx->d_sites, d_lens, n_seq, DyadTilesOf{});
   if (both_strands) {
     PENGK_HIP(hipFuncSetAttribute((const void*)dyad_count_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(dyad_count_kernel<true>, grid, dim3(DYAD_THREADS), lds, ctx->stream, d_words, d_valid, d_offs, d_lens, n_seq,
-                       n_gaps, per_group, excl, boff, n_groups, (unsigned long long*)d_counts, (unsigned long long*)d_mono);
+                       n_gaps, per_group, plan.excl, plan.boff, plan.n_groups, (unsigned long long*)d_counts, (unsigned long long*)d_mono);
   } else {
     PENGK_HIP(hipFuncSetAttribute((const void*)dyad_count_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(dyad_count_kernel<false>, grid, dim3(DYAD_THREADS), lds, ctx->stream, d_words, d_valid, d_offs, d_lens, n_seq,
-                       n_gaps, per_group, excl, boff, n_groups, (unsigned long long*)d_counts, (unsigned long long*)d_mono);
+                       n_gaps, per_group, plan.excl, plan.boff, plan.n_groups, (unsigned long long*)d_counts, (unsigned long long*)d_mono);
   }
   PENGK_HIP(hipGetLastError());
   return PENGK_OK;

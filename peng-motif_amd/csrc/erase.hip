@@ -16,18 +16,12 @@
 
 #include "pengk_internal.h"
 #include "scan_walk.h"
+#include "tile_walk.h"
 
 namespace pengk {
 namespace {
 
 using namespace scan;
-
-// validity word j of a sequence of L bases under the caller's words vp (NULL: every base valid); bits at and beyond L: 0
-__device__ __forceinline__ uint32_t valid_word(const uint32_t* vp, uint32_t L, uint32_t j) {
-  const uint32_t rem = L - 32u * j;
-  const uint32_t in = rem >= 32u ? 0xFFFFFFFFu : ((1u << rem) - 1u);
-  return vp ? vp[j] & in : in;
-}
 
 // ---- pengk_mask_sites -------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void mask_init_kernel(const uint32_t* __restrict__ valid, const int64_t* __restrict__ offs,
@@ -36,7 +30,7 @@ __global__ __launch_bounds__(256) void mask_init_kernel(const uint32_t* __restri
   for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n_seq; i += (uint64_t)gridDim.x * blockDim.x) {
     const uint32_t L = lens[i];
     const uint64_t w0 = (uint64_t)offs[i] >> 5;
-    for (uint32_t j = 0; 32ull * j < L; ++j) out[w0 + j] = valid_word(valid ? valid + w0 : nullptr, L, j);
+    for (uint32_t j = 0; 32ull * j < L; ++j) out[w0 + j] = tile::valid_word_in(valid ? valid + w0 : nullptr, L, j);
   }
 }
 
@@ -137,11 +131,11 @@ enum { TOT_WINDOWS = 0, TOT_BOUND, TOT_MAX_LEN, TOT_NOT_WHOLE, TOT_BASES, TOT_IT
 // the first position >= i of a sequence of L bases that holds no valid base (L: none); vp NULL: every base valid
 __device__ __forceinline__ uint64_t first_invalid(const uint32_t* vp, uint32_t L, uint64_t i) {
   if (!vp) return L;
-  uint32_t k = (uint32_t)(i >> 5);
-  uint32_t inv = ~valid_word(vp, L, k) >> (i & 31u);
+  uint32_t k = (uint32_t)(i >> 5);  // (i < L: word k exists, here and below)
+  uint32_t inv = ~tile::valid_word_in(vp, L, k) >> (i & 31u);
   if (inv) return i + (uint32_t)__builtin_ctz(inv);  // (a bit at or beyond L reads as invalid: never past L)
   for (++k; 32ull * k < L; ++k) {
-    inv = ~valid_word(vp, L, k);
+    inv = ~tile::valid_word_in(vp, L, k);
     if (inv) return 32ull * k + (uint32_t)__builtin_ctz(inv);
   }
   return L;

@@ -135,6 +135,11 @@ __host__ __device__ inline uint32_t revcomp32(uint32_t id, int W) {
   return v >> (32 - 2 * W);
 }
 
+// Where the table of order k stands among the (k+1)-mer tables of orders 0 .. K laid end to end, (4^(k+1) - 4) / 3: the
+// counters that bg_order.hip writes and the model that stats_order.hip reads.  0, 4, 20, 84, 340, 1364, 5460
+__host__ __device__ constexpr uint32_t order_table_at(int k) { return ((1u << (2 * (k + 1))) - 4u) / 3u; }
+static_assert(order_table_at(3) == 84u && order_table_at(6) == 5460u, "the tables' places");
+
 // The splitmix64 finalizer: every counter-based draw of the library (the synthetic inputs, the background sampler, the
 // best-site tie-break keys, the hold-out split).
 __host__ __device__ __forceinline__ uint64_t mix64(uint64_t x) {

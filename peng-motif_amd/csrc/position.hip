@@ -1,10 +1,9 @@
 // position.hip -- k-mers with a position bias counted on the device (--positional): the table defined in
 // include/pengk.h ("positional words").
 //
-//   tile     64 consecutive positions of one sequence, one wave, one position per lane.  A lane reads the 16 bases from
-//            q = max(p - (K-1), 0) on (its own word and the K-1 <= 6 words that may stand before it lie in the first
-//            2K-1 <= 13 of them: two 32-bit halves of the layout's words, one funnel shift) and the validity bits from q
-//            on; st = v & v>>1 & .. & v>>(K-1) says for every base of the window whether a word stands there.  Standing,
+//   tile     64 consecutive positions of one sequence, one wave, one position per lane.  A lane reads the window of
+//            tile_walk.h with K-1 bases behind it (its own word and the K-1 <= 6 words that may stand before it lie in
+//            the first 2K-1 <= 13 of its 16 bases) and the validity bits from the window's start on; st = v & v>>1 & .. & v>>(K-1) says for every base of the window whether a word stands there.  Standing,
 //            clump head, coordinate and bin are decided in registers, in 32-bit arithmetic throughout.
 //   clumps   two words have the same key iff the code of one is the code of the other or, on both strands, its reverse
 //            complement: no predecessor is folded, each is compared with the lane's code and its reverse complement.
@@ -16,9 +15,9 @@
 //            empty bins add nothing, so no entry that is not canonical is ever written.
 //   tiles    only the tiles of a sequence that hold a position whose coordinate lies under bin_size * n_bins are walked:
 //            one contiguous range of them under every anchor (a superset is taken: the lane decides).  Their counts per
-//            sequence -> exclusive sums (two small launches), then every wave of a fixed grid takes one contiguous share
-//            of the tiles, as dyad.hip does: static, every wave of the grid runs the same number of rounds, so the
-//            barriers of the flush sit in workgroup-uniform control flow.  A tile none of whose positions can fall into
+//            sequence -> exclusive sums, then every wave of a fixed grid walks one contiguous share of the tiles: the
+//            plan, the share and the cursor of tile_walk.h.  Every wave of the grid runs the same number of rounds, so
+//            the barriers of the flush sit in workgroup-uniform control flow.  A tile none of whose positions can fall into
 //            the workgroup's bins is left before anything is loaded (one range of a sequence under start and end, two
 //            under centre).
 //   wrap     a position bumps at most one bin of a workgroup once, a round holds at most 1024 positions, and the tables are
@@ -29,6 +28,7 @@
 #include <vector>
 
 #include "pengk_internal.h"
+#include "tile_walk.h"
 
 namespace pengk {
 namespace {
@@ -37,7 +37,6 @@ constexpr int POS_THREADS = 1024;
 constexpr int POS_WAVES = POS_THREADS / 64;
 constexpr int POS_LDS_BINS = 1 << 15;            // uint32 bins a workgroup holds at most: 128 KiB
 constexpr uint32_t POS_FLUSH_ROUNDS = 1u << 21;  // x 1024 positions a round = 2^31 per bin at most
-constexpr int POS_SCAN_THREADS = 256;
 static_assert(POS_LDS_BINS * 4 <= 160 * 1024, "a group's tables fit in LDS");
 static_assert(2 * PENGK_POSITION_MAX_K - 1 <= 16, "a position's words lie in one window of 16 bases");
 static_assert((uint64_t)PENGK_POSITION_MAX_BIN_SIZE * PENGK_POSITION_MAX_BINS <= (1ull << 22), "the coordinates under test fit 32 bits");
@@ -69,57 +68,11 @@ __host__ __device__ __forceinline__ PosTiles pos_tiles(uint32_t L, int K, int an
   return t;
 }
 
-__device__ __forceinline__ uint32_t pos_valid_word(const uint32_t* vp, uint32_t L, uint32_t nw, uint32_t j) {
-  if (j >= nw) return 0u;
-  const uint32_t rem = L - 32u * j;
-  const uint32_t in = rem >= 32u ? 0xFFFFFFFFu : ((1u << rem) - 1u);
-  return vp ? vp[j] & in : in;
-}
-
-// ---- tile counts and their exclusive sums (the scheme of dyad.hip) ------------------------------------------------------
-__device__ __forceinline__ unsigned long long pos_group_inclusive_sum(unsigned long long v, unsigned long long* sh) {
-  const int t = threadIdx.x;
-  sh[t] = v;
-  __syncthreads();
-  for (int d = 1; d < POS_SCAN_THREADS; d <<= 1) {
-    const unsigned long long x = t >= d ? sh[t - d] : 0ull;
-    __syncthreads();
-    sh[t] += x;
-    __syncthreads();
-  }
-  const unsigned long long r = sh[t];
-  __syncthreads();
-  return r;
-}
-
-// excl[i]: the tiles of the sequences in front of i within its group of 256; boff[b]: the tiles of group b
-__global__ __launch_bounds__(POS_SCAN_THREADS) void pos_tiles_kernel(const uint32_t* __restrict__ lens, uint64_t n_seq, int K, int anchor,
-                                                                     uint32_t R, unsigned long long* __restrict__ excl,
-                                                                     unsigned long long* __restrict__ boff) {
-  __shared__ unsigned long long sh[POS_SCAN_THREADS];
-  const uint64_t i = (uint64_t)blockIdx.x * POS_SCAN_THREADS + threadIdx.x;
-  const unsigned long long nt = i < n_seq ? pos_tiles(lens[i], K, anchor, R).nt : 0u;
-  const unsigned long long incl = pos_group_inclusive_sum(nt, sh);
-  if (i < n_seq) excl[i] = incl - nt;
-  if (threadIdx.x == POS_SCAN_THREADS - 1) boff[blockIdx.x] = incl;
-}
-
-// boff[0 .. n_groups) -> exclusive sums in place, boff[n_groups] = the total; one workgroup
-__global__ __launch_bounds__(POS_SCAN_THREADS) void pos_groups_kernel(unsigned long long* __restrict__ boff, uint64_t n_groups) {
-  __shared__ unsigned long long sh[POS_SCAN_THREADS];
-  unsigned long long carry = 0;
-  for (uint64_t b = 0; b < n_groups; b += POS_SCAN_THREADS) {
-    const uint64_t k = b + threadIdx.x;
-    const unsigned long long v = k < n_groups ? boff[k] : 0ull;
-    const unsigned long long incl = pos_group_inclusive_sum(v, sh);
-    if (k < n_groups) boff[k] = carry + incl - v;
-    sh[threadIdx.x] = incl;  // (the last thread's is the chunk's total)
-    __syncthreads();
-    carry += sh[POS_SCAN_THREADS - 1];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) boff[n_groups] = carry;
-}
+struct PosTilesOf {
+  int K, anchor;
+  uint32_t R;
+  __device__ __forceinline__ PosTiles operator()(uint32_t L) const { return pos_tiles(L, K, anchor, R); }
+};
 
 // ---- the count ----------------------------------------------------------------------------------------------------------
 // the coordinate of position p <= D in a sequence whose last position is D.  32 bits throughout: with h = D >> 1 and
@@ -150,16 +103,9 @@ __device__ __forceinline__ void pos_tile(const uint64_t* __restrict__ wp, const 
   }
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t p = (k << 6) + lane;  // (k < 2^26)
-  const uint32_t q = p >= (uint32_t)(K - 1) ? p - (uint32_t)(K - 1) : 0u;
-  const uint32_t off = p - q;  // the lane's own place in its window: K-1 but at the sequence's start
-  // the words as halves of 16 bases: the 2K-1 <= 13 bases from q on lie in the half of q and the next one
-  const uint32_t* hp = reinterpret_cast<const uint32_t*>(wp);
-  const uint32_t nh = (L + 15u) >> 4, h = q >> 4;
-  const uint32_t H0 = h < nh ? hp[h] : 0u, H1 = h + 1u < nh ? hp[h + 1u] : 0u;
-  const uint32_t lo = __builtin_amdgcn_alignbit(H1, H0, (q & 15u) << 1);  // the 16 bases from q on
-  const uint32_t nw = (L + 31u) >> 5, j = q >> 5;
-  const uint32_t V0 = pos_valid_word(vp, L, nw, j), V1 = pos_valid_word(vp, L, nw, j + 1u);
-  const uint32_t v = __builtin_amdgcn_alignbit(V1, V0, q & 31u);  // the validity bits of the 32 bases from q on
+  // the window from q = max(p - (K-1), 0) on: the lane's word and the K-1 that may stand before it, 2K-1 <= 13 bases
+  const tile::Window win = tile::window(wp, vp, L, p, (uint32_t)(K - 1));
+  const uint32_t lo = win.lo, v = win.v, off = win.off;
   uint32_t st = v;  // bit i: a word stands at q + i
 #pragma unroll
   for (int d = 1; d < K; ++d) st &= v >> d;
@@ -215,53 +161,22 @@ __global__ __launch_bounds__(POS_THREADS) void pos_count_kernel(const uint64_t* 
   extern __shared__ __attribute__((aligned(16))) uint32_t sh[];  // (b1 - b0) tables
   const int b0 = (int)blockIdx.y * per_group, b1 = std::min(n_bins, b0 + per_group), nb = b1 - b0;
   const uint32_t c0 = (uint32_t)b0 * S, c1 = (uint32_t)b1 * S, R = (uint32_t)n_bins * S;
-  // this wave's share of the tiles: [g, gend); `per` rounds for every wave of the grid
-  const uint64_t total = boff[n_groups];
-  const uint64_t n_waves = (uint64_t)gridDim.x * POS_WAVES;
-  const uint64_t per = (total + n_waves - 1) / n_waves;
-  if ((uint64_t)blockIdx.x * POS_WAVES * per >= total) return;  // (the whole workgroup: nothing to zero, nothing to flush)
+  // this wave's share of the tiles; `per` rounds for every wave of the grid
+  const tile::Share share = tile::share<POS_WAVES>(boff, n_groups);
+  if (share.block_empty) return;  // (the whole workgroup: nothing to zero, nothing to flush)
   for (int q = threadIdx.x; q < nb * NK; q += POS_THREADS) sh[q] = 0u;
   __syncthreads();
-  const uint64_t wave = (uint64_t)blockIdx.x * POS_WAVES + (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  uint64_t g = wave * per;
-  const uint64_t gend = g + per < total ? g + per : total;
-  uint64_t i = 0;
-  uint32_t k = 0, L = 0;
-  PosTiles t = {0u, 0u};
-  if (g < gend) {
-    // the sequence and the tile of it that g is: the last group with boff <= g, the last sequence of it with excl <= rest
-    uint64_t lo = 0, hi = n_groups;  // boff[lo] <= g < boff[hi]
-    while (hi - lo > 1) {
-      const uint64_t mid = lo + (hi - lo) / 2;
-      if (boff[mid] <= g) lo = mid;
-      else hi = mid;
-    }
-    const uint64_t rest = g - boff[lo];
-    i = lo * POS_SCAN_THREADS;
-    uint64_t ihi = std::min<uint64_t>(n_seq, i + POS_SCAN_THREADS);
-    while (ihi - i > 1) {
-      const uint64_t mid = i + (ihi - i) / 2;
-      if (excl[mid] <= rest) i = mid;
-      else ihi = mid;
-    }
-    k = (uint32_t)(rest - excl[i]);
-    L = lens[i];
-    t = pos_tiles(L, K, anchor, R);
-  }
+  uint64_t g = share.g;
+  tile::Cursor<PosTilesOf> c{lens, n_seq, PosTilesOf{K, anchor, R}};
+  if (g < share.gend) c.locate(g, excl, boff, n_groups);
   uint32_t since = 0;
-  for (uint64_t round = 0; round < per; ++round) {  // (per, and so every barrier below, is the same for the whole grid)
-    if (g < gend) {
-      while (k >= t.nt) {  // the next sequence that has a tile (there is one: g < total)
-        if (++i >= n_seq) break;
-        L = lens[i];
-        t = pos_tiles(L, K, anchor, R);
-        k = 0;
+  for (uint64_t round = 0; round < share.per; ++round) {  // (per, and so every barrier below, is the same for the whole grid)
+    if (g < share.gend) {
+      if (c.next()) {
+        const uint64_t w0 = (uint64_t)offs[c.i] >> 5;
+        pos_tile<K, BOTH>(words + w0, valid ? valid + w0 : nullptr, c.L, c.t.k0 + c.k, anchor, S, c0, c1, sh);
       }
-      if (i < n_seq) {
-        const uint64_t w0 = (uint64_t)offs[i] >> 5;
-        pos_tile<K, BOTH>(words + w0, valid ? valid + w0 : nullptr, L, t.k0 + k, anchor, S, c0, c1, sh);
-      }
-      ++k;
+      ++c.k;
       ++g;
     }
     if (++since == POS_FLUSH_ROUNDS) {
@@ -308,14 +223,9 @@ __device__ __forceinline__ void pos_pair_tile(const uint64_t* __restrict__ wp, c
   if (P0 > D) return;
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t p = P0 + lane;
-  // the 16 bases and the validity bits of the 32 bases from p on: the word at p is the first K <= 7 of them
-  const uint32_t* hp = reinterpret_cast<const uint32_t*>(wp);
-  const uint32_t nh = (L + 15u) >> 4, h = p >> 4;
-  const uint32_t H0 = h < nh ? hp[h] : 0u, H1 = h + 1u < nh ? hp[h + 1u] : 0u;
-  const uint32_t lo = __builtin_amdgcn_alignbit(H1, H0, (p & 15u) << 1);
-  const uint32_t nw = (L + 31u) >> 5, j = p >> 5;
-  const uint32_t V0 = pos_valid_word(vp, L, nw, j), V1 = pos_valid_word(vp, L, nw, j + 1u);
-  const uint32_t v = __builtin_amdgcn_alignbit(V1, V0, p & 31u);
+  // the window from p on: the word at p is the first K <= 7 of its bases
+  const tile::Window win = tile::window(wp, vp, L, p, 0u);
+  const uint32_t lo = win.lo, v = win.v;
   const uint32_t c = p <= D ? pos_coordinate(anchor, p, D) : R;
   const uint32_t bin = c < R ? c / S : POS_NO_BIN;
   const bool on = bin != POS_NO_BIN && (v & ALL) == ALL;  // (a word that stands ends inside the sequence: p <= D)
@@ -364,52 +274,22 @@ __global__ __launch_bounds__(POS_THREADS) void pos_pairs_kernel(const uint64_t* 
   __shared__ uint32_t tab[PENGK_POSITION_MAX_BINS * 16];
   const int n_tab = n_bins * 16;
   const uint32_t R = (uint32_t)n_bins * S;
-  // this wave's share of the tiles, as in pos_count_kernel: [g, gend); `per` rounds for every wave of the grid
-  const uint64_t total = boff[n_groups];
-  const uint64_t n_waves = (uint64_t)gridDim.x * POS_WAVES;
-  const uint64_t per = (total + n_waves - 1) / n_waves;
-  if ((uint64_t)blockIdx.x * POS_WAVES * per >= total) return;  // (the whole workgroup)
+  // this wave's share of the tiles, as in pos_count_kernel; `per` rounds for every wave of the grid
+  const tile::Share share = tile::share<POS_WAVES>(boff, n_groups);
+  if (share.block_empty) return;  // (the whole workgroup)
   for (int q = threadIdx.x; q < n_tab; q += POS_THREADS) tab[q] = 0u;
   __syncthreads();
-  const uint64_t wave = (uint64_t)blockIdx.x * POS_WAVES + (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  uint64_t g = wave * per;
-  const uint64_t gend = g + per < total ? g + per : total;
-  uint64_t i = 0;
-  uint32_t k = 0, L = 0;
-  PosTiles t = {0u, 0u};
-  if (g < gend) {
-    uint64_t lo = 0, hi = n_groups;  // boff[lo] <= g < boff[hi]
-    while (hi - lo > 1) {
-      const uint64_t mid = lo + (hi - lo) / 2;
-      if (boff[mid] <= g) lo = mid;
-      else hi = mid;
-    }
-    const uint64_t rest = g - boff[lo];
-    i = lo * POS_SCAN_THREADS;
-    uint64_t ihi = std::min<uint64_t>(n_seq, i + POS_SCAN_THREADS);
-    while (ihi - i > 1) {
-      const uint64_t mid = i + (ihi - i) / 2;
-      if (excl[mid] <= rest) i = mid;
-      else ihi = mid;
-    }
-    k = (uint32_t)(rest - excl[i]);
-    L = lens[i];
-    t = pos_tiles(L, K, anchor, R);
-  }
+  uint64_t g = share.g;
+  tile::Cursor<PosTilesOf> c{lens, n_seq, PosTilesOf{K, anchor, R}};
+  if (g < share.gend) c.locate(g, excl, boff, n_groups);
   uint32_t since = 0;
-  for (uint64_t round = 0; round < per; ++round) {  // (per, and so every barrier below, is the same for the whole grid)
-    if (g < gend) {
-      while (k >= t.nt) {  // the next sequence that has a tile (there is one: g < total)
-        if (++i >= n_seq) break;
-        L = lens[i];
-        t = pos_tiles(L, K, anchor, R);
-        k = 0;
+  for (uint64_t round = 0; round < share.per; ++round) {  // (per, and so every barrier below, is the same for the whole grid)
+    if (g < share.gend) {
+      if (c.next()) {
+        const uint64_t w0 = (uint64_t)offs[c.i] >> 5;
+        pos_pair_tile<K, BOTH>(words + w0, valid ? valid + w0 : nullptr, c.L, c.t.k0 + c.k, anchor, S, R, tab);
       }
-      if (i < n_seq) {
-        const uint64_t w0 = (uint64_t)offs[i] >> 5;
-        pos_pair_tile<K, BOTH>(words + w0, valid ? valid + w0 : nullptr, L, t.k0 + k, anchor, S, R, tab);
-      }
-      ++k;
+      ++c.k;
       ++g;
     }
     if (++since == POS_PAIR_FLUSH_ROUNDS) {
@@ -431,14 +311,9 @@ int pos_pairs_launch(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_
   return PENGK_OK;
 }
 
-// the argument checks, enter(ctx) and the two prefix-sum launches that pengk_position_count and pengk_position_pairs share:
-// scratch = excl (n_seq uint64) | boff (n_groups + 1 uint64)
-struct PosPlan {
-  unsigned long long *excl, *boff;
-  uint64_t n_groups;
-};
+// the argument checks, enter(ctx) and the plan of the tiles (tile_walk.h) that pengk_position_count and pengk_position_pairs share
 int pos_prepare(pengk_ctx* ctx, const char* fn, const uint64_t* d_words, const int64_t* d_offs, const uint32_t* d_lens, uint64_t n_seq, int K,
-                int anchor, int bin_size, int n_bins, int both_strands, const uint64_t* d_table, PosPlan* plan) {
+                int anchor, int bin_size, int n_bins, int both_strands, const uint64_t* d_table, tile::Plan* plan) {
   if (!ctx || (n_seq && (!d_words || !d_offs || !d_lens || !d_table))) return fail(PENGK_ERR_ARG, "%s: bad argument", fn);
   if (K < PENGK_POSITION_MIN_K || K > PENGK_POSITION_MAX_K)
     return fail(PENGK_ERR_ARG, "%s: K %d out of range [%d,%d]", fn, K, PENGK_POSITION_MIN_K, PENGK_POSITION_MAX_K);
@@ -452,14 +327,9 @@ int pos_prepare(pengk_ctx* ctx, const char* fn, const uint64_t* d_words, const i
   int rc = enter(ctx);
   if (rc) return rc;
   if (n_seq == 0) return PENGK_OK;
-  plan->n_groups = (n_seq + POS_SCAN_THREADS - 1) / POS_SCAN_THREADS;
-  rc = ensure_scratch(ctx, &ctx->d_sites, &ctx->sites_bytes, (n_seq + plan->n_groups + 1) * sizeof(uint64_t));
+  rc = ensure_scratch(ctx, &ctx->d_sites, &ctx->sites_bytes, tile::plan_bytes(n_seq));
   if (rc) return rc;
-  plan->excl = (unsigned long long*)ctx->d_sites;
-  plan->boff = plan->excl + n_seq;
-  hipLaunchKernelGGL(pos_tiles_kernel, dim3((unsigned)plan->n_groups), dim3(POS_SCAN_THREADS), 0, ctx->stream, d_lens, n_seq, K, anchor,
-                     (uint32_t)bin_size * (uint32_t)n_bins, plan->excl, plan->boff);
-  hipLaunchKernelGGL(pos_groups_kernel, dim3(1), dim3(POS_SCAN_THREADS), 0, ctx->stream, plan->boff, plan->n_groups);
+  *plan = tile::plan(ctx, ctx->d_sites, d_lens, n_seq, PosTilesOf{K, anchor, (uint32_t)bin_size * (uint32_t)n_bins});
   return PENGK_OK;
 }
 
@@ -478,7 +348,7 @@ extern "C" {
 
 int pengk_position_count(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_valid, const int64_t* d_offs, const uint32_t* d_lens,
                          uint64_t n_seq, int K, int anchor, int bin_size, int n_bins, int both_strands, uint64_t* d_counts) {
-  PosPlan plan;
+  tile::Plan plan;
   const int rc = pos_prepare(ctx, "pengk_position_count", d_words, d_offs, d_lens, n_seq, K, anchor, bin_size, n_bins, both_strands, d_counts,
                              &plan);
   if (rc || n_seq == 0) return rc;
@@ -500,7 +370,7 @@ int pengk_position_count(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t
 
 int pengk_position_pairs(pengk_ctx* ctx, const uint64_t* d_words, const uint32_t* d_valid, const int64_t* d_offs, const uint32_t* d_lens,
                          uint64_t n_seq, int K, int anchor, int bin_size, int n_bins, int both_strands, uint64_t* d_pairs) {
-  PosPlan plan;
+  tile::Plan plan;
   const int rc = pos_prepare(ctx, "pengk_position_pairs", d_words, d_offs, d_lens, n_seq, K, anchor, bin_size, n_bins, both_strands, d_pairs,
                              &plan);
   if (rc || n_seq == 0) return rc;

@@ -16,7 +16,6 @@ namespace {
 using namespace sweep;
 
 constexpr int SO_MAX_K = 5;
-__host__ __device__ constexpr uint32_t so_at(int k) { return ((1u << (2 * (k + 1))) - 4u) / 3u; }  // 0, 4, 20, 84, 340, 1364, 5460
 
 // the order-K probability of pattern x (digits x_0 .. x_{W-1}, x_0 lowest) from the tables sVK
 template <int W>
@@ -28,7 +27,7 @@ __device__ __forceinline__ float order_product(uint32_t x, const float* __restri
     const int c = i < K ? i : K;
     const uint32_t d = (x >> (2 * i)) & 3u;
     word = ((word << 2) | d) & ((1u << (2 * (c + 1))) - 1u);
-    p *= sVK[so_at(c) + word];
+    p *= sVK[order_table_at(c) + word];
   }
   return p;
 }
@@ -40,9 +39,9 @@ __global__ __launch_bounds__(256) void stats_order_kernel(int both, int k, int m
                                                           float* __restrict__ expected, float* __restrict__ logp,
                                                           float* __restrict__ z, const Ctrl... ctrl_arg) {
   __shared__ float sV[84];
-  extern __shared__ __attribute__((aligned(16))) float sVK[];  // so_at(K + 1) floats
+  extern __shared__ __attribute__((aligned(16))) float sVK[];  // order_table_at(K + 1) floats
   if (threadIdx.x < 84) sV[threadIdx.x] = V[threadIdx.x];
-  const uint32_t nv = so_at(K + 1);
+  const uint32_t nv = order_table_at(K + 1);
   for (uint32_t t = threadIdx.x; t < nv; t += blockDim.x) sVK[t] = VK[t];
   __syncthreads();
   constexpr uint32_t NP = 1u << (2 * W);
@@ -95,7 +94,7 @@ int launch_w(pengk_ctx* ctx, int both, int k, int max_k, const float* d_V, int K
   const uint32_t np = 1u << (2 * W);
   const uint32_t need = (np + 255) / 256;
   const uint32_t cap = (uint32_t)ctx->num_cu * 16u;
-  hipLaunchKernelGGL((stats_order_kernel<W, Ctrl...>), dim3(need < cap ? need : cap), dim3(256), so_at(K + 1) * sizeof(float),
+  hipLaunchKernelGGL((stats_order_kernel<W, Ctrl...>), dim3(need < cap ? need : cap), dim3(256), order_table_at(K + 1) * sizeof(float),
                      ctx->stream, both, k, max_k, d_V, K, d_VK, (const unsigned long long*)d_ltot, d_counts, d_bgprob, d_expected,
                      d_logp, d_z, ctrl...);
   PENGK_HIP(hipGetLastError());

@@ -1,9 +1,8 @@
 // strata.hip -- the background counters of every GC stratum of a scan layout (pengk_strata_bg_count,
 // --stratified-background): 84 (k+1)-mer counters a stratum and its windows, in one pass over the words.
 //
-//   tile     64 consecutive positions of one sequence, one wave, one position per lane, as position.hip reads them: the
-//            16 bases from q = max(p - 2, 0) on (two 32-bit halves of the layout's words, one funnel shift) and the 32
-//            validity bits from q on.  The lane's key is the 3-mer ending at p in BaMM order -- its low 4 bits are the
+//   tile     64 consecutive positions of one sequence, one wave, one position per lane: the window of tile_walk.h with
+//            two bases behind the position, 16 bases and 32 validity bits from q = max(p - 2, 0) on.  The lane's key is the 3-mer ending at p in BaMM order -- its low 4 bits are the
 //            2-mer, its low 2 bits the base -- and three flags say which of the three orders stand there.
 //   counts   no atomic per base.  Six ballots give the key's bits over the wave; lane b selects the lanes whose key is
 //            b (six ands of a ballot or its complement) and counts them under the three flags' ballots with a
@@ -18,6 +17,7 @@
 // d_bg holds n_strata x 84 uint64 and is ADDED to; nothing else is written but d_windows.
 #include "pengk_internal.h"
 #include "scan_walk.h"
+#include "tile_walk.h"
 
 namespace pengk {
 namespace {
@@ -28,13 +28,6 @@ constexpr int SBG_ROW = 85;                      // 84 counters and the stratum'
 constexpr uint32_t SBG_FLUSH_TILES = 1u << 25;   // x 64 positions = 2^31 per counter at most between two flushes
 constexpr int SBG_PER_CU = 4;                    // workgroups a CU: 32 waves (16 strata take 43.5 KB of LDS each: three)
 static_assert(SBG_WAVES * 16 * SBG_ROW * 4 <= 64 * 1024, "a workgroup's histograms fit in the LDS a launch may ask for");
-
-__device__ __forceinline__ uint32_t sbg_valid_word(const uint32_t* vp, uint32_t L, uint32_t nw, uint32_t j) {
-  if (j >= nw) return 0u;
-  const uint32_t rem = L - 32u * j;
-  const uint32_t in = rem >= 32u ? 0xFFFFFFFFu : ((1u << rem) - 1u);
-  return vp ? vp[j] & in : in;
-}
 
 __device__ __forceinline__ unsigned long long sbg_pick(unsigned long long ballot, uint32_t bit) { return bit ? ballot : ~ballot; }
 
@@ -79,20 +72,12 @@ __global__ __launch_bounds__(SBG_THREADS) void strata_bg_kernel(const uint64_t* 
     const uint64_t w0 = (uint64_t)offs[i] >> 5;
     const uint64_t* wp = words + w0;
     const uint32_t* vp = valid ? valid + w0 : nullptr;
-    const uint32_t* hp = reinterpret_cast<const uint32_t*>(wp);
-    const uint32_t nh = (L + 15u) >> 4, nw = (L + 31u) >> 5;
     const uint32_t n_tiles = ((L - 1u) >> 6) + 1u;
     uint32_t c1 = 0, c2 = 0, c3 = 0, win = 0;  // (a sequence holds fewer than 2^32 positions)
     for (uint32_t t = 0; t < n_tiles; ++t) {
       const uint32_t p = (t << 6) + lane;  // (p < L + 64: L <= 2^32 - 64 is checked by no one; p wraps only beyond it)
-      const uint32_t q = p >= 2u ? p - 2u : 0u;
-      const uint32_t off = p - q;  // the lane's own place in its window: 2 but at the sequence's start
-      const uint32_t h = q >> 4;
-      const uint32_t H0 = h < nh ? hp[h] : 0u, H1 = h + 1u < nh ? hp[h + 1u] : 0u;
-      const uint32_t lo = __builtin_amdgcn_alignbit(H1, H0, (q & 15u) << 1);  // the 16 bases from q on
-      const uint32_t j = q >> 5;
-      const uint32_t V0 = sbg_valid_word(vp, L, nw, j), V1 = sbg_valid_word(vp, L, nw, j + 1u);
-      const uint32_t v = __builtin_amdgcn_alignbit(V1, V0, q & 31u);  // the validity bits of the 32 bases from q on
+      const tile::Window w = tile::window(wp, vp, L, p, 2u);
+      const uint32_t lo = w.lo, v = w.v, off = w.off;  // (off: 2 but at the sequence's start)
       // the bases x_{p-2} x_{p-1} x_p, older base more significant; what lies before the sequence reads as A and stands nowhere
       const uint32_t three = lo & 63u;  // first base lowest
       const uint32_t x0 = three & 3u, x1 = (three >> 2) & 3u, x2 = three >> 4;
